@@ -16,12 +16,16 @@ Launching: `python bench.py --gpus N` with no WORLD_SIZE in the environment star
 under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`); started under
 torch.distributed.run it uses the ranks it is given.  Either way rank 0 prints ONE JSON line.
 
-The line (contract in the task statement): value = sentences of the whole job per second, `roofline` (dominant kernel,
+A plain run sets up, warms up, times the steps and prints the line: value = sentences of the whole job per second, `ms_per_step` =
+milliseconds one timed step took.  --dump-outputs DIR also writes what the last timed step computed (dump_outputs below).
+
+--full adds everything else the line can carry, none of it ever `value`: `parity_vs_oracle_sample` (a sample of the timed batch
+against the oracle, bit-exact), `roofline` (dominant kernel,
 algorithmic bytes from the oracle's event counters / hipEvent kernel time, measured on rank 0's shard), `cpu_baseline` (the C
 restatement of vibrato's CPU path in oracle/, timed on this host: the whole batch at N = 1, a 20k-sentence sample of rank 0's
-shard at N > 1) and, at N = 1, three legs that are never `value`: `suite` (BASELINE config 5 and the dense lexicon law through
+shard at N > 1) and, at N = 1, `two_batches_in_flight` and three legs: `suite` (BASELINE config 5 and the dense lexicon law through
 the same timed loop), `worker_loop` (the reference's per-sentence 3-call loop through Worker), `host_to_host` and `format`
-(text in -> MeCab-format text out, next to the oracle's tokenize + print loop).
+(text in -> MeCab-format text out, next to the oracle's tokenize + print loop).  The --no-* options drop single legs of a --full run.
 """
 import argparse
 import json
@@ -97,6 +101,34 @@ def self_launch(args):
     return subprocess.call(cmd, env=env, cwd=ROOT)
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs writes at most this much (float64 elements)
+DUMP_SEED = 20240229    # of the sentence sample, where the whole output is larger
+
+
+def dump_outputs(dirpath, parts):
+    """--dump-outputs: what the last timed step left for its caller, as float64 .npy files under `dirpath`.  `parts`: (tok_off, tok_cnt,
+    tokens) of every shard, in corpus order.  tok_cnt.npy: the token count of every sentence.  tokens.npy: [k, 6] token records (the
+    fields of TOKEN_DTYPE, in its order) of the sentences that sentences.npy lists, in sentence order -- the device hands out token
+    ranges in arrival order, so tok_off itself differs from run to run and is not written.  Every sentence is listed if that fits
+    DUMP_BYTES; otherwise a fixed sample: the longest prefix of a seeded permutation of the sentences that fits."""
+    from vibrato_amd import TOKEN_DTYPE, sharding
+    cnt = np.concatenate([c for _, c, _ in parts]).astype(np.int64)
+    n = len(cnt)
+    order = np.random.default_rng(DUMP_SEED).permutation(n)
+    room = (DUMP_BYTES - 16 * n) // (8 * len(TOKEN_DTYPE.names))  # token records next to tok_cnt and sentences (8 bytes a sentence each)
+    pick = np.sort(order[:int(np.searchsorted(np.cumsum(cnt[order]), room, side="right"))])
+    rows, base = [], 0
+    for off, c, toks in parts:
+        sel = pick[(pick >= base) & (pick < base + len(c))] - base
+        t, _ = sharding.tokens_in_sentence_order(off[sel], c[sel], toks)
+        rows.append(np.stack([t[f].astype(np.float64) for f in TOKEN_DTYPE.names], axis=1))
+        base += len(c)
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "tok_cnt.npy"), cnt.astype(np.float64))
+    np.save(os.path.join(dirpath, "sentences.npy"), pick.astype(np.float64))
+    np.save(os.path.join(dirpath, "tokens.npy"), np.concatenate(rows))
+
+
 def timed_leg(tok, text, offs, steps, warmup, torch):
     """The timed loop of one single-GPU leg (device-resident input, results left in HBM): returns (seconds, stats)."""
     n, nbytes = len(offs) - 1, int(len(text))
@@ -127,6 +159,10 @@ def main():
     ap.add_argument("--dict", default="unidic", choices=["tiny", "small", "small-dense", "ipadic", "unidic", "unidic-dense"])
     ap.add_argument("--sentences", type=int, default=0, help="sentences of the whole job (default: 100000 at --gpus 1 = config 3, "
                                                              "1000000 at --gpus N > 1 = config 4)")
+    ap.add_argument("--full", action="store_true", help="also everything that is never `value`: the parity gate against the oracle, roofline, CPU "
+                                                        "baselines, two batches in flight and the legs the --no-* options name (default: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                                                                        "(float64; a fixed seeded sample of the sentences where the whole is larger)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--ignore-space", action="store_true")
     ap.add_argument("--max-grouping-len", type=int, default=0)
@@ -141,6 +177,8 @@ def main():
     ap.add_argument("--no-suite", action="store_true", help="skip the extra single-GPU legs (BASELINE config 5, dense lexicon law); never `value`")
     ap.add_argument("--no-worker-loop", action="store_true", help="skip the per-sentence Worker leg (the reference's 3-call loop); never `value`")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -328,13 +366,24 @@ def main():
             gathered_ok = sum(sent_by_rank) == n_total and tok_by_rank[rank] == total_tokens
             total_tokens = sum(tok_by_rank)
 
+    if args.dump_outputs and rank == 0:
+        if world > 1:  # the gathered slots of the last step: every rank's shard, in corpus order
+            last = gather["out"][(gather["k"] - 1) & 1].view(world, -1)
+            parts = [sharding.unpack_results(last[r], gather["max_s"])[2:] for r in range(world)]
+        else:
+            v = sharding.workspace_views(ws, n, total_tokens)
+            parts = [(v["tok_off"].cpu().numpy().view(np.uint32), v["tok_cnt"].cpu().numpy().view(np.uint32),
+                      v["tokens"].cpu().numpy().view(V.TOKEN_DTYPE))]
+        dump_outputs(args.dump_outputs, parts)
+        del parts
+
     kernel_ms = st["ms_tier0"] + st["ms_tier12"] + st["ms_pack"]
 
     # two batches in flight (two workspaces on two streams, the same resident input): what a caller that streams batches gets when the
     # tail of one batch's kernels runs under the head of the next one's.  Outside the timed region and never `value`: a step of
     # `value` is one batch at a time on one stream, which is also what the roofline's kernel durations are measured on.
     two_in_flight = None
-    if world == 1 and not args.no_suite:
+    if args.full and world == 1 and not args.no_suite:
         wsp = [tok.workspace(n, nbytes) for _ in range(2)]
         stp = [torch.cuda.Stream() for _ in range(2)]
         for i in range(4):
@@ -353,7 +402,7 @@ def main():
     # host-to-host leg, outside the timed region and never `value`: what a caller of the batched entry
     # point pays -- the copy of the text into the batch, H2D, kernels, D2H of the token records into host memory
     h2h = None
-    if not args.no_host_pipeline and world == 1:
+    if args.full and not args.no_host_pipeline and world == 1:
         h2h = {"one_call": tok.host_pipeline_benchmark(text, offs, threads=1, rounds=1, repeats=6),
                "pipelined": tok.host_pipeline_benchmark(text, offs, threads=4, rounds=4),
                "pipelined_8_threads": tok.host_pipeline_benchmark(text, offs, threads=8, rounds=4)}
@@ -372,7 +421,11 @@ def main():
         h2h["fixed_ms_per_additional_device"] = round((h2h["one_call_device_list_0x8"]["ms_per_batch"] - h2h["one_call_device_list_0x4"]["ms_per_batch"]) / 4, 4)
 
     result = None
-    if rank == 0:
+    workload = (f"{sd.name} ({sd.n_words} words, {sd.num_right}x{sd.num_left} i16 matrix = "
+                f"{sd.num_right * sd.num_left * 2 / 2**20:.1f} MiB), {n_total} sentences {args.law} chars, "
+                f"{total_bytes_all} bytes, seed {synth.SEED}")
+    parity = roofline = cpu = cpu_all = worker_loop = fmt = suite = None
+    if rank == 0 and args.full:
         from oracle import oracle as ora  # checker + cpu_baseline leg only
         import tempfile
         native_dir = tempfile.mkdtemp(prefix="vbt_oracle_")
@@ -410,9 +463,6 @@ def main():
         b_gen = b_alg - b_lat
         ms_gen, ms_lat = st["ms_tier0"], st["ms_tier12"]
         achieved = b_lat / (ms_lat * 1e-3) if ms_lat > 0 else 0.0
-        workload = (f"{sd.name} ({sd.n_words} words, {sd.num_right}x{sd.num_left} i16 matrix = "
-                    f"{sd.num_right * sd.num_left * 2 / 2**20:.1f} MiB), {n_total} sentences {args.law} chars, "
-                    f"{total_bytes_all} bytes, seed {synth.SEED}")
         tr = committed_counters(workload) if world == 1 else None
         trk = (tr or {}).get("hbm_bytes_by_kernel", {})
         ins = (tr or {}).get("wave_insts_by_kernel", {})
@@ -608,6 +658,7 @@ def main():
                               "parity_vs_oracle_sample": okx, "parity_sample_sentences": nsx, "leg_s": round(time.time() - t_leg, 1)}
                 del tokx, dvx, dox, wx, tx, ox
 
+    if rank == 0:
         value = n_total * args.steps / elapsed
         par = (f"dp{world}: {n_total}-sentence corpus in {world} contiguous shards balanced by bytes, one process per GPU, no data-path "
                f"collective; final device-resident gather of the packed results ({'to every rank: all_gather_into_tensor' if args.gather == 'all' else 'to rank 0: grouped send/recv'}, {backend}), overlapped with the next step"
@@ -629,8 +680,10 @@ def main():
                        "ignore_space": args.ignore_space, "max_grouping_len": args.max_grouping_len, "user_lexicon_words": args.user_lexicon,
                        "connection_ids_reordered": reorder_info, "parallelism": par},
             "parity_vs_oracle_sample": parity, "tokens_per_step": total_tokens, "lattice_density_candidates_per_byte": round(tok.lattice_density(), 3),
-            "parity_gate": "this run compared a 5 000-sentence sample of the timed batch (3 000 per suite leg) and the formatter's bytes with the oracle; the "
-                           "full-size comparisons (configs 2, 3, 5 and the dense law: every record of 100 000 sentences) are tests/test_gpu_parity.py",
+            "parity_gate": ("this run compared a 5 000-sentence sample of the timed batch (3 000 per suite leg) and the formatter's bytes with the oracle; the "
+                            "full-size comparisons (configs 2, 3, 5 and the dense law: every record of 100 000 sentences) are tests/test_gpu_parity.py"
+                            if args.full else "not run (--full); every record of 100 000 sentences per configuration is compared in tests/test_gpu_parity.py"),
+            "full": args.full,
             "per_rank": per_rank,
             "gather": ({"bytes_per_rank_slot": gather["slot"], "collective": "all_gather_into_tensor" if args.gather == "all" else "gather to rank 0 (grouped send/recv)", "device_resident": True,
                         "delivered_all_shards": bool(gathered_ok)} if world > 1 else None),
@@ -644,7 +697,7 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and result and not result["parity_vs_oracle_sample"]:
+    if rank == 0 and result and result["parity_vs_oracle_sample"] is False:
         raise SystemExit("PARITY FAILURE vs oracle")
 
 

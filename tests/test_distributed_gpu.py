@@ -101,7 +101,7 @@ def test_bench_py_multi_rank_path_runs_config4_shape():
     env = dict(os.environ, VBT_BENCH_BACKEND="gloo", VBT_BENCH_SINGLE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     port = 29600 + (os.getpid() % 2000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--dict", "small", "--sentences", "20000"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -127,7 +127,7 @@ def test_bench_py_launches_its_own_ranks_without_a_launcher():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(VBT_BENCH_BACKEND="gloo", VBT_BENCH_SINGLE_DEVICE="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dict", "small", "--sentences", "20000"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--dict", "small", "--sentences", "20000"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     _check_multi_rank_line(p.stdout)

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for rep in 1 2; do for v in "" nogather samecell; do
   for extra in "" "--dict unidic-dense"; do
     echo -n "variant '$v' $extra: "
-    VBT_LIB_VARIANT=$v timeout 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop $extra 2>&1 | grep '^{' | tail -1 | python -c "
+    VBT_LIB_VARIANT=$v timeout 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop $extra 2>&1 | grep '^{' | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['roofline']
 print('lattice ms', r['kernel_ms'], 'gen ms', r['gen_candidates']['kernel_ms'], 'step ms', d['ms_per_step'], 'parity', d['parity_vs_oracle_sample'])"

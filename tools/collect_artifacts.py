@@ -38,7 +38,7 @@ if os.path.exists(p_prev):  # keep the hand-written notes under the table
     notes = txt[k:] if k >= 0 else ""
 open(p_prev, "w").write(
     f"# Round {tag[1:].lstrip('0')}: bench lines of the other BASELINE configurations (tools/round_artifacts.sh {tag}, one MI355X, device-resident)\n\n"
-    "`python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 10 <args>`; full JSON lines in "
+    "`python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 10 <args>`; full JSON lines in "
     f"gpurun_out/art_{tag}/ (scratch).\nThe default `python bench.py` line (profiles/{tag}_bench_default.json) carries config 5 and the dense law as `suite` legs as well.\n\n"
     "| run | sentences/s | ms per step | generator ms | lattice ms (fork to join) | fallback + packing ms | nodes / dedup pairs per char | "
     "sentences: segment tier, escape launches, fallback | bit-exact sample |\n|---|---|---|---|---|---|---|---|---|\n" + "\n".join(rows) + "\n" + notes)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # config 5 (long sentences in segments): which lean / segment tier pair with the five-wave slim instance?
-B="python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 20 --warmup 3 --law mixed --ignore-space --max-grouping-len 24 --user-lexicon 1000"
+B="python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 20 --warmup 3 --law mixed --ignore-space --max-grouping-len 24 --user-lexicon 1000"
 pick='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of VBT_FILL_ROUNDS (gen_one's hit expansion: rounds of 64 hits requested together): variant libraries f1 / f2 / f4, alternating on one box.
 #   build first:  python -c "from vibrato_amd.build import build; [build(variant='f%d' % r, defines=['VBT_FILL_ROUNDS=%d' % r]) for r in (1, 2, 4)]"
-B="python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 20 --warmup 3"
+B="python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 20 --warmup 3"
 pick='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

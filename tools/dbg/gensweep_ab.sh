@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of VBT_GEN_SWEEP (generator + lean sweep in one wave) on the headline, config 5 and the dense law: alternating runs on one box.
-B="python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 20 --warmup 3"
+B="python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 20 --warmup 3"
 pick='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

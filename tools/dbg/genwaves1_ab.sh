@@ -1,4 +1,4 @@
-B="python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 30 --warmup 3"
+B="python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 30 --warmup 3"
 pick='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

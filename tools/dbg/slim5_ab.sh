@@ -2,7 +2,7 @@
 # The slim instance of the sweep at five waves per SIMD (variant library s5: -DVBT_SLIM_WAVES=5, 96 VGPRs) with an 8 KiB segment tier
 # (20 per CU) against the default (four waves, 10 KiB, 16 per CU), alternating on one box.
 #   build first: python -c "from vibrato_amd.build import build; build(variant='s5', defines=['VBT_SLIM_WAVES=5'])"
-B="python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps ${STEPS:-30} --warmup 3"
+B="python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps ${STEPS:-30} --warmup 3"
 pick='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # s5 library: which lean tier in front of an 8 KiB segment tier?  headline, short sentences, ipadic.
-B="python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 30 --warmup 3"
+B="python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 30 --warmup 3"
 pick='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Lean instance at six waves per SIMD (80 VGPRs): tier sets with a 6.5 KiB lean tier against the 8 KiB one, alternating on one box.
-B="python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps ${STEPS:-40} --warmup 3"
+B="python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps ${STEPS:-40} --warmup 3"
 pick='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # two lean tiers in front of the 8 KiB segment tier (final build of round 6): does the second lean tier still cost the generator what it saves the sweep?
-B="python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 30 --warmup 3"
+B="python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 30 --warmup 3"
 pick='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

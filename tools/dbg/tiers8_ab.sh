@@ -1,6 +1,6 @@
 #!/bin/bash
 # lean tiers on one side stream: which sets?  headline, short sentences, config 5, dense law (dense: 10 KiB segments)
-B="python bench.py --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 30 --warmup 3"
+B="python bench.py --full --no-cpu-baseline --no-host-pipeline --no-suite --no-worker-loop --steps 30 --warmup 3"
 pick='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):

@@ -19,7 +19,7 @@ if os.path.exists(f"{src}/bench_line.json") and os.path.getsize(f"{src}/bench_li
 stats = glob.glob(f"{src}/stats/**/*kernel_stats.csv", recursive=True)
 if stats:
     shutil.copyfile(stats[0], f"profiles/{tag}_kernel_stats.csv")
-    lines += [f"## `rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-pipeline` (profiles/{tag}_kernel_stats.csv)\n",
+    lines += [f"## `rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-pipeline` (profiles/{tag}_kernel_stats.csv)\n",
               "| kernel | calls | total ms | avg us | min us | max us | % |", "|---|---|---|---|---|---|---|"]
     for r in csv.DictReader(open(stats[0])):
         lines.append(f"| `{r['Name'][:70]}` | {r['Calls']} | {float(r['TotalDurationNs']) / 1e6:.3f} | {float(r['AverageNs']) / 1e3:.1f} | "
