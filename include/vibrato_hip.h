@@ -261,6 +261,17 @@ VBT_API int vbt_batch_format(const vbt_batch* b, int mode, char** out, size_t* l
  * already, or from somewhere else) is ignored.  Big buffers are kept for the next call (at most 4 / 512 MiB per process) until
  * vbt_tokenizer_trim_pool or vbt_tokenizer_free. */
 VBT_API void vbt_free(void* p);
+/* Host text in -> wakati text out (tokenize/src/main.rs:96-103: the surfaces of a sentence joined by ' ', then '\n'; "\n" for a
+ * sentence without tokens; the lines of the n sentences back to back), rendered ON THE DEVICE: the same bytes as vbt_tokenize_batch +
+ * vbt_batch_format(VBT_FORMAT_WAKATI), but no token records are packed or copied and no host thread formats anything -- the text goes
+ * in, two kernels behind the sweeps write the lines (vbt_workspace_set_wakati), the 8-byte total comes back and exactly that many
+ * bytes are copied into a pinned block (by the SDMA engine vbt_tokenize_batch uses): about a quarter of the bytes the records are.
+ * *out is released ONLY with vbt_free, like vbt_batch_format's; line_off (optional): n + 1 entries, line s is
+ * out[line_off[s] .. line_off[s + 1]), line_off[n] = *len.  Input contract and error codes as vbt_tokenize_batch (VBT_ERR_UTF8, ...).
+ * One unpipelined call on a pooled workspace; thread-safe per tokenizer.  A multi-device tokenizer (vbt_tokenizer_new_multi with more than
+ * one device) is refused with VBT_ERR_UNSUPPORTED: sharded rendering is not implemented. */
+VBT_API int vbt_tokenize_wakati(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
+                                char** out, size_t* len, uint64_t* line_off);
 
 /* ---- Device-resident API (zero-copy; what bench.py times) ------------------------ */
 
@@ -302,15 +313,28 @@ VBT_API int vbt_workspace_results(const vbt_workspace* ws, const vbt_token_rec**
  * back to the workspace's own buffers.  vbt_workspace_results then points into the slot.  The caller alternates two slots to
  * overlap the gather of batch k with the kernels of batch k + 1. */
 VBT_API int vbt_workspace_set_packed_output(vbt_workspace* ws, void* d_slot, uint64_t slot_bytes, uint64_t max_sentences);
+/* Wakati output on the device.  While enabled, every vbt_tokenize_batch_device call of this workspace also renders the segmented
+ * text of its batch -- line s = the surfaces of sentence s joined by ' ', then '\n' -- into a buffer the workspace owns (allocated
+ * when the mode is first enabled: 2 max_bytes + max_sentences bytes, the bound of bytes + tokens + sentences), straight from the
+ * sweeps' per-sentence staging: the token records are NOT packed (vbt_workspace_results is then undefined except tok_cnt and the
+ * total) unless keep_records is set.  A wave renders a sentence VBT_WAKATI_ROUND tokens at a time.
+ * enabled: 0 = off, 1 = on, a value > 1 = on with the output limited to that many bytes (callers that budget device memory, tests):
+ * a line that would end beyond the limit sets error flag 32 and is not written, the lines in front of it are.  The 64 bytes behind
+ * the capacity belong to the buffer and are never written.
+ * vbt_workspace_wakati: d_out = the lines back to back, d_line_off = u64[n + 1] byte offsets of the lines, d_line_off[n] = bytes
+ * written; device pointers, valid once the stream of the call has been synchronized. */
+#define VBT_WAKATI_ROUND 256
+VBT_API int vbt_workspace_set_wakati(vbt_workspace* ws, int enabled, int keep_records);
+VBT_API int vbt_workspace_wakati(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off /* n + 1 */);
 /* Per-call statistics (synchronizes the stream of the last call): how many sentences were filed
  * in the LDS tiers sentences are routed to up front -- the lean tier and the segment tier (n_tier0) --, in the escape tiers behind
  * them (n_tier1: what a sweep passed on) and in the list of the global-memory fallback kernel (n_tier2; a re-routed sentence is
  * counted in every list it was filed in), tokens
  * written, device error flags (1 = token buffer full, 2 = scratch exhausted, 4 = sentence too
- * long, 8 = bad offsets, 16 = invalid UTF-8) and, with timing enabled, the hipEvent-measured durations (ms, on the launch stream) of the
+ * long, 8 = bad offsets, 16 = invalid UTF-8, 32 = a wakati line did not fit the output buffer) and, with timing enabled, the hipEvent-measured durations (ms, on the launch stream) of the
  * input check and the candidate generators (ms_tier0: validate_batch, gen_candidates, build_lists, the gen_long levels), of the
  * lattice sweeps from their fork to their join (ms_tier12) and of what follows -- the global-memory fallback launch and the packing
- * of the token records (ms_pack). */
+ * of the token records and, in wakati mode, the three kernels that render the lines (ms_pack). */
 typedef struct vbt_call_stats {
     uint64_t n_sentences, n_tier0, n_tier1, n_tier2, n_tokens;
     uint32_t error_flags;

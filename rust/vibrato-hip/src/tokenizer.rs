@@ -145,6 +145,24 @@ impl Tokenizer {
         Ok(Batch::from_raw(raw, self))
     }
 
+    /// Wakati output of many sentences (`tokenize/src/main.rs:96-103`: surfaces joined by one space, one line per sentence),
+    /// rendered on the device (new): the bytes of `tokenize_batch(..)?.format(OutputMode::Wakati)` without token records or host
+    /// formatter threads. Returns the text and the `n + 1` byte offsets of its lines. Single-device tokenizers only.
+    pub fn tokenize_wakati_raw(&self, text: &[u8], offsets: &[u64]) -> Result<(String, Vec<u64>)> {
+        if offsets.is_empty() || *offsets.last().unwrap() as usize > text.len() {
+            return Err(VibratoError::invalid_argument("offsets", "offsets must hold n + 1 positions inside text"));
+        }
+        let (mut p, mut n): (*mut std::os::raw::c_char, usize) = (ptr::null_mut(), 0);
+        let mut line_off = vec![0u64; offsets.len()];
+        check(unsafe {
+            sys::vbt_tokenize_wakati(self.raw()?, text.as_ptr(), offsets.as_ptr(), (offsets.len() - 1) as u64, &mut p, &mut n, line_off.as_mut_ptr())
+        })?;
+        // Safety: the surfaces are slices of validated UTF-8 cut at character boundaries, the separators ASCII
+        let s = unsafe { std::str::from_utf8_unchecked(std::slice::from_raw_parts(p as *const u8, n)) }.to_owned();
+        unsafe { sys::vbt_free(p as *mut _) };
+        Ok((s, line_off))
+    }
+
     /// The per-line loop of the reference's callers (`tokenize/src/main.rs:78-95`) over an iterator of lines, batched behind the
     /// scenes (new): lines are collected until `batch_bytes` of text (or `batch_lines` lines) are in hand, tokenized as ONE device
     /// batch, and handed back one sentence at a time in input order. `Worker::tokenize` costs ~35 us per call on the GPU (one

@@ -330,6 +330,29 @@ class Tokenizer:
                                            len(offsets) - 1, C.byref(h)))
         return Batch(self, h)
 
+    def tokenize_wakati(self, sentences=None, text=None, offsets=None, with_offsets=False):
+        """Host text in -> wakati text out (tokenize/src/main.rs:96-103), rendered on the device (vbt_tokenize_wakati): the bytes of
+        tokenize_batch(...).format("wakati") without token records or host formatter threads.  Returns bytes, or with
+        `with_offsets` (bytes, np.uint64[n + 1]): line s is out[line_off[s]:line_off[s + 1]].  Single-device tokenizers only."""
+        if sentences is not None:
+            enc = [_b(s) for s in sentences]
+            offsets = np.zeros(len(enc) + 1, dtype=np.uint64)
+            if enc:
+                offsets[1:] = np.cumsum([len(e) for e in enc])
+            text = np.frombuffer(b"".join(enc), dtype=np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        line_off = np.zeros(n + 1, dtype=np.uint64) if with_offsets else None
+        p, ln = C.c_void_p(), C.c_size_t()
+        N.check(N.lib().vbt_tokenize_wakati(self._handle(), text.ctypes.data if text.size else None, offsets.ctypes.data, n, C.byref(p), C.byref(ln),
+                                            line_off.ctypes.data if with_offsets else None))
+        try:
+            out = C.string_at(p, ln.value)
+        finally:
+            N.lib().vbt_free(p)
+        return (out, line_off) if with_offsets else out
+
     def tokenize_lines(self, lines, batch_bytes=16 << 20, batch_lines=100000):
         """The per-line loop of the reference's callers (tokenize/src/main.rs:78-95) over an iterable of lines, batched behind the
         scenes: lines are collected until `batch_bytes` of text (or `batch_lines` lines) are in hand, tokenized as ONE device batch and
@@ -676,6 +699,17 @@ class Workspace:
         final gather (sharding.packed_bytes / unpack_results): no copy kernels between the tokenizer and the collective.
         slot_ptr=None: back to the workspace's own buffers."""
         N.check(N.lib().vbt_workspace_set_packed_output(self._h, slot_ptr or None, int(slot_bytes), int(max_sentences)))
+
+    def set_wakati(self, on=True, keep_records=False, _out_cap=None):
+        """Every later run() also renders the batch's wakati text on the device (wakati_ptrs); the token records are packed only
+        with keep_records.  _out_cap (tests): the kernels may use that many bytes (> 1) of the output buffer only."""
+        N.check(N.lib().vbt_workspace_set_wakati(self._h, (int(_out_cap) if _out_cap is not None else 1) if on else 0, int(keep_records)))
+
+    def wakati_ptrs(self):
+        """Device addresses {"out": the lines back to back, "line_off": u64[n + 1], line_off[n] = bytes written} of the last run()."""
+        o, lo = C.c_void_p(), C.c_void_p()
+        N.check(N.lib().vbt_workspace_wakati(self._h, C.byref(o), C.byref(lo)))
+        return {"out": o.value, "line_off": lo.value}
 
     def result_ptrs(self):
         p = [C.c_void_p() for _ in range(4)]

@@ -14,6 +14,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -341,6 +342,7 @@ void check_device_errors(uint32_t flags) {
     if (flags & kErrTokCap) throw Error(VBT_ERR_INVALID_STATE, "device token buffer overflow");
     if (flags & kErrScratch) throw Error(VBT_ERR_UNSUPPORTED, "device scratch arena exhausted (raise VBT_SCRATCH_MB)");
     if (flags & kErrTooLong) throw Error(VBT_ERR_UNSUPPORTED, "sentence too long for the device image (>= 4 GiB or >= 2^32 lattice nodes)");
+    if (flags & kErrWakatiCap) throw Error(VBT_ERR_INVALID_STATE, "device wakati buffer overflow");
 }
 
 // Token accessors (token.rs:21-92) from a raw record.
@@ -543,11 +545,48 @@ void* out_alloc(size_t bytes) {
     return h + 1;
 }
 
+// The same contract for buffers that are filled by the GPU's copy engines (vbt_tokenize_wakati): whole pinned blocks, registered by
+// their address; vbt_free keeps the last few for the next call (pinning a block costs milliseconds) under the same limits.
+std::unordered_map<const void*, std::unique_ptr<PinnedBlock>> g_pin_live;
+std::vector<std::unique_ptr<PinnedBlock>> g_pin_cache;
+
+void* pin_out_alloc(size_t bytes) {
+    std::unique_ptr<PinnedBlock> b;
+    {
+        std::lock_guard<std::mutex> g(g_out_mu);
+        size_t best = g_pin_cache.size();
+        for (size_t i = 0; i < g_pin_cache.size(); ++i)
+            if (g_pin_cache[i]->cap >= bytes && (best == g_pin_cache.size() || g_pin_cache[i]->cap < g_pin_cache[best]->cap)) best = i;
+        if (best != g_pin_cache.size()) {
+            b = std::move(g_pin_cache[best]);
+            g_pin_cache.erase(g_pin_cache.begin() + (long)best);
+        }
+    }
+    if (!b) {
+        b = std::make_unique<PinnedBlock>();
+        b->cap = round_up_pow2(bytes + bytes / 8, 1 << 16);  // (head room: the next batch's output is about as long)
+        HIPX(hipHostMalloc(&b->p, b->cap, hipHostMallocPortable | hipHostMallocMapped));
+    }
+    void* p = b->p;
+    std::lock_guard<std::mutex> g(g_out_mu);
+    g_pin_live.emplace(p, std::move(b));
+    return p;
+}
+
 void out_free(void* p) {
     if (!p) return;
     OutHeader* h = nullptr;
+    std::unique_ptr<PinnedBlock> drop;  // (hipHostFree synchronises the device: outside the lock)
     {
         std::lock_guard<std::mutex> g(g_out_mu);
+        if (auto it = g_pin_live.find(p); it != g_pin_live.end()) {
+            drop = std::move(it->second);
+            g_pin_live.erase(it);
+            uint64_t held = drop->cap;
+            for (const auto& q : g_pin_cache) held += q->cap;
+            if (g_pin_cache.size() < kOutCacheSlots && held <= kOutCacheMaxTotal) g_pin_cache.push_back(std::move(drop));
+            return;
+        }
         if (g_out_live.erase(p) == 0) return;  // not a live buffer of this library: freed already, or never ours
         h = static_cast<OutHeader*>(p) - 1;
         if (h->cap >= kOutCacheMinBytes) {
@@ -561,9 +600,11 @@ void out_free(void* p) {
 
 void out_cache_trim() {
     std::vector<OutHeader*> drop;
+    std::vector<std::unique_ptr<PinnedBlock>> pinned;
     {
         std::lock_guard<std::mutex> g(g_out_mu);
         drop.swap(g_out_cache);
+        pinned.swap(g_pin_cache);
     }
     for (OutHeader* h : drop) std::free(h);
 }
@@ -1093,6 +1134,24 @@ int vbt_worker_token(const vbt_worker* w, uint32_t i, vbt_token* out) {
 
 // Splits n sentences into `parts` contiguous ranges balanced by bytes (vibrato_amd/sharding.py: shard_bounds, the rule the
 // multi-process path uses): range k ends at the first sentence that starts at or behind k / parts of the text.
+// VBT_H2H_OUT, decided once per tokenizer (the replicas' Sdma objects are created here): true = results leave the device on the SDMA engines
+static bool results_by_sdma(vbt_tokenizer* tok) {
+    if (tok->out_mode.load(std::memory_order_acquire) < 0) {
+        std::lock_guard<std::mutex> g(tok->pool_mu);
+        if (tok->out_mode.load(std::memory_order_relaxed) < 0) {
+            const char* e = std::getenv("VBT_H2H_OUT");
+            int mode = e && *e ? std::atoi(e) : 1;
+            if (mode == 1)
+                for (auto& r : tok->reps) {
+                    r->sdma = std::make_unique<Sdma>(r->t->device());
+                    if (!r->sdma->ok) mode = 0;
+                }
+            tok->out_mode.store(mode, std::memory_order_release);  // (behind the Sdma objects: a thread that sees the mode sees them)
+        }
+    }
+    return tok->out_mode.load(std::memory_order_acquire) == 1;
+}
+
 static void shard_bounds(const uint64_t* offs, uint64_t n, uint32_t parts, std::vector<uint64_t>& bounds) {
     bounds.assign(parts + 1, n);
     bounds[0] = 0;
@@ -1173,20 +1232,7 @@ int vbt_tokenize_batch(const vbt_tokenizer* tok_, const uint8_t* text, const uin
         // How the results reach the host (VBT_H2H_OUT): 1 (default) = packed on the device, then copied by the GPU's SDMA engines
         // (Sdma above); 0 = the packing kernel stores them straight into this batch's pinned block.  Either way the total and the
         // error flags come back first, in 8 bytes, so that the pinned block is sized exactly.
-        if (tok->out_mode.load(std::memory_order_acquire) < 0) {
-            std::lock_guard<std::mutex> g(tok->pool_mu);
-            if (tok->out_mode.load(std::memory_order_relaxed) < 0) {
-                const char* e = std::getenv("VBT_H2H_OUT");
-                int mode = e && *e ? std::atoi(e) : 1;
-                if (mode == 1)
-                    for (auto& r : tok->reps) {
-                        r->sdma = std::make_unique<Sdma>(r->t->device());
-                        if (!r->sdma->ok) mode = 0;
-                    }
-                tok->out_mode.store(mode, std::memory_order_release);  // (behind the Sdma objects: a thread that sees the mode sees them)
-            }
-        }
-        const bool use_sdma = tok->out_mode.load(std::memory_order_acquire) == 1;
+        const bool use_sdma = results_by_sdma(tok);
         auto note_ratio = [&](uint64_t total) {  // tokens per KiB, rounded up: the largest seen
             if (!bytes) return;
             const uint32_t r = (uint32_t)std::min<uint64_t>(0xFFFFFFu, (total * 1024 + bytes - 1) / bytes + 1);
@@ -1444,6 +1490,92 @@ int vbt_tokenize_batch(const vbt_tokenizer* tok_, const uint8_t* text, const uin
             pool_give(tok, *tok->reps[k], std::move(s.p));
         });
         *out = h.b.release();
+    });
+}
+
+// Text in -> wakati text out, rendered on the device (wakati.hip).  One unpipelined call: the text and its offsets go in, the
+// launch sequence of the batch ends with the wakati kernels instead of the record packing, 16 bytes come back ({tokens, error
+// flags}, the output's length), then exactly that many bytes and line_off[] leave the device on the copy engine.
+int vbt_tokenize_wakati(const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len, uint64_t* line_off) {
+    return guarded([&] {
+        vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
+        if (!tok || !offsets || !out || !len || (!text && n && offsets[n] != offsets[0])) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (tok->reps.size() > 1) throw Error(VBT_ERR_UNSUPPORTED, "vbt_tokenize_wakati: a multi-device tokenizer cannot render wakati output (sharded rendering is not implemented)");
+        const uint64_t lo = offsets[0];
+        for (uint64_t i = 1; i <= n; ++i)
+            if (offsets[i] < offsets[i - 1]) throw Error(VBT_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
+        const uint64_t bytes = offsets[n] - lo;
+        if (bytes >= 0xFFFFFFFFull || n >= 0xFFFFFFFFull) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch too large (split it)");
+        if (n == 0) {
+            void* p = out_alloc(0);
+            if (!p) throw std::bad_alloc();
+            *out = static_cast<char*>(p); *len = 0;
+            if (line_off) line_off[0] = 0;
+            return;
+        }
+        Replica& rep = *tok->reps[0];
+        const bool use_sdma = results_by_sdma(tok);
+        struct Holder {  // the block and the workspace go back to their pools on every path, the workspace in record mode
+            vbt_tokenizer* tok;
+            Replica& rep;
+            std::unique_ptr<PinnedBlock> blk;
+            std::unique_ptr<PooledWorkspace> p;
+            void* result = nullptr;  // handed to the caller at the end, released here on a failure
+            ~Holder() {
+                if (p) {
+                    (void)hipSetDevice(rep.t->device());
+                    (void)hipStreamSynchronize(p->stream);
+                    p->ws->set_wakati(false, false);
+                    pool_give(tok, rep, std::move(p));
+                }
+                host_give(tok, std::move(blk));
+                if (result) out_free(result);
+            }
+        } h{tok, rep, nullptr, nullptr};
+        // pinned: [n + 1 rebased offsets][text, padded to 8][{tokens u32, error flags u32}, total u64][n + 1 line offsets]
+        const size_t text_end = (n + 1) * 8 + ((bytes + 7) & ~(uint64_t)7);
+        h.blk = host_take(tok, text_end + 16 + (n + 1) * 8);
+        uint64_t* offs = static_cast<uint64_t*>(h.blk->p);
+        uint8_t* txt = reinterpret_cast<uint8_t*>(offs + n + 1);
+        uint32_t* tail = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(h.blk->p) + text_end);
+        uint64_t* total = reinterpret_cast<uint64_t*>(tail + 2);
+        uint64_t* loff = total + 1;
+        for (uint64_t i = 0; i <= n; ++i) offs[i] = offsets[i] - lo;
+        if (bytes) std::memcpy(txt, text + lo, bytes);
+        tail[0] = tail[1] = 0; *total = 0;
+        HIPX(hipSetDevice(rep.t->device()));
+        h.p = pool_take(tok, rep, n, bytes);
+        PooledWorkspace& p = *h.p;
+        p.ws->set_wakati(true, false);
+        if (bytes) HIPX(hipMemcpyAsync(p.d_text, txt, bytes, hipMemcpyHostToDevice, p.stream));
+        HIPX(hipMemcpyAsync(p.d_off, offs, (n + 1) * 8, hipMemcpyHostToDevice, p.stream));
+        p.ws->run(static_cast<const uint8_t*>(p.d_text), p.d_off, n, bytes, p.stream);
+        HIPX(hipMemcpyAsync(tail, p.ws->d_ctrl, 8, hipMemcpyDeviceToHost, p.stream));
+        HIPX(hipMemcpyAsync(total, p.ws->d_line_off + n, 8, hipMemcpyDeviceToHost, p.stream));
+        HIPX(hipStreamSynchronize(p.stream));
+        if (tail[1] & kErrUtf8) {
+            for (uint64_t i = 0; i < n; ++i)
+                if (!valid_utf8(txt + offs[i], offs[i + 1] - offs[i])) throw Error(VBT_ERR_UTF8, "sentence " + std::to_string(i) + " is not valid UTF-8");
+        }
+        check_device_errors(tail[1]);
+        const size_t out_bytes = (size_t)*total;
+        h.result = pin_out_alloc(out_bytes);
+        const void* src[2] = {p.ws->d_wakati, p.ws->d_line_off};
+        void* dst[2] = {h.result, loff};
+        const size_t sz[2] = {out_bytes, line_off ? (size_t)(n + 1) * 8 : 0};
+        if (use_sdma) {
+            std::vector<hsa_signal_t> sigs;
+            bool ok = rep.sdma->issue(src, dst, sz, 2, sigs);
+            ok = Sdma::wait(sigs) && ok;
+            if (!ok) throw Error(VBT_ERR_DEVICE, "device -> host copy of the wakati text failed (hsa_amd_memory_async_copy)");
+        } else {
+            for (int k = 0; k < 2; ++k)
+                if (sz[k]) HIPX(hipMemcpyAsync(dst[k], src[k], sz[k], hipMemcpyDeviceToHost, p.stream));
+            HIPX(hipStreamSynchronize(p.stream));
+        }
+        if (line_off) std::memcpy(line_off, loff, (n + 1) * 8);
+        *out = static_cast<char*>(h.result); *len = out_bytes;
+        h.result = nullptr;
     });
 }
 
@@ -1726,6 +1858,22 @@ int vbt_workspace_set_packed_output(vbt_workspace* ws, void* d_slot, uint64_t sl
     return guarded([&] {
         if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
         ws->w->set_packed_output(d_slot, slot_bytes, max_sentences);
+    });
+}
+
+int vbt_workspace_set_wakati(vbt_workspace* ws, int enabled, int keep_records) {
+    return guarded([&] {
+        if (!ws || enabled < 0) throw Error(VBT_ERR_INVALID_ARGUMENT, "null workspace or negative `enabled`");
+        ws->w->set_wakati(enabled != 0, keep_records != 0, enabled > 1 ? (uint64_t)enabled : 0);
+    });
+}
+
+int vbt_workspace_wakati(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off) {
+    return guarded([&] {
+        if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (!ws->w->d_wakati) throw Error(VBT_ERR_INVALID_STATE, "wakati output was never enabled on this workspace (vbt_workspace_set_wakati)");
+        if (d_out) *d_out = ws->w->d_wakati;
+        if (d_line_off) *d_line_off = ws->w->d_line_off;
     });
 }
 

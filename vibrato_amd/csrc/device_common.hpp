@@ -83,6 +83,20 @@ __device__ __forceinline__ uint32_t wave_inscan_max_dpp(uint32_t x) {
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)wave_inscan_dpp(v), 63); }
 __device__ __forceinline__ uint32_t wave_umax(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)wave_inscan_max_dpp(v), 63); }
 
+// exclusive prefix sum over a workgroup of whole waves (warp_sums: one word per wave); every thread gets the workgroup's total
+__device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t* warp_sums, uint32_t& block_total) {
+    uint32_t wtot;
+    const uint32_t ex = wave_exscan_any(v, wtot);
+    const uint32_t w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if ((threadIdx.x & 63u) == 0) warp_sums[w] = wtot;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+    for (uint32_t i = 0; i < nw; ++i) { const uint32_t t = warp_sums[i]; if (i < w) base += t; tot += t; }
+    __syncthreads();
+    block_total = tot;
+    return base + ex;
+}
+
 // Packed lattice key: high word = min_cost biased to unsigned order (cost ^ 0x80000000), low word =
 // 0xFFFFFFFE - insertion sequence number.  Unsigned-minimum over keys = minimum cost with ties broken
 // towards the LAST inserted node, the `<=` rule of search_min_node (lattice.rs:141-146).  Adding a

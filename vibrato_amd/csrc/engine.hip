@@ -440,6 +440,12 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
     if (packed_slot && n > packed_max_s) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch has more sentences than the packed output slot holds");
     if (n == 0) {
         if (packed_slot) HIP_CHECK(hipMemsetAsync(packed_slot, 0, 32, stream));  // header of an empty result
+        if (wakati) {  // no lines: line_off[0] = 0
+            BatchArgs a{};
+            a.ctrl = d_ctrl;
+            kern::wakati_lines(stream, a, 0, d_line_len, d_wakati_tiles, d_line_off, d_wakati, wakati_cap, false);
+            HIP_CHECK(hipGetLastError());
+        }
         return;
     }
     // this batch's tiers: the workspace's, except that a batch of short sentences (at most 96 bytes on average: nearly every lattice fits)
@@ -651,8 +657,11 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
         // (the totals per tile were added up by the kernels that emitted the tokens; their prefix is taken inside compact_tokens
         // unless the batch is huge or the caller packs later and wants the grand total first)
         const bool scan_kernel = defer_pack || n_tiles > 2048 || env_u32("VBT_PACK_SCAN", 0);
-        if (scan_kernel) kern::tok_tile_scan(stream, a, d_tile_sums, n_tiles);
-        if (!defer_pack) kern::compact_tokens(stream, a, d_tile_sums, n_tiles, scan_kernel ? 1u : 0u);
+        // (wakati mode: the lines are rendered from the staging regions; the records are packed only for a caller who wants both)
+        const bool records = !wakati || wakati_keep;
+        if (wakati) kern::wakati_lines(stream, a, n_tiles, d_line_len, d_wakati_tiles, d_line_off, d_wakati, wakati_cap, !records);
+        if (records && scan_kernel) kern::tok_tile_scan(stream, a, d_tile_sums, n_tiles);
+        if (records && !defer_pack) kern::compact_tokens(stream, a, d_tile_sums, n_tiles, scan_kernel ? 1u : 0u);
         last_args = a;
     }
     rec(2);
@@ -690,6 +699,30 @@ void Workspace::set_packed_output(void* slot, uint64_t slot_bytes, uint64_t max_
         if (slot_bytes < 32 + 8 * max_s) throw Error(VBT_ERR_INVALID_ARGUMENT, "packed output: the slot is smaller than its header and per-sentence arrays");
     }
     packed_slot = slot; packed_bytes = slot ? slot_bytes : 0; packed_max_s = slot ? max_s : 0;
+}
+
+void Workspace::set_wakati(bool on, bool keep_records, uint64_t cap_limit) {
+    if (on && !d_wakati) {
+        HIP_CHECK(hipSetDevice(tok.device()));
+        const uint64_t ns = std::max<uint64_t>(max_sentences, 1), cap = 2 * max_bytes + ns;  // bytes + tokens (<= bytes) + a byte per sentence
+        auto alloc = [&](size_t bytes) {
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, bytes));
+            pipe_allocs.push_back(p);
+            return p;
+        };
+        // (nothing to clear: every word the caller may read is written by the kernels of the batch)
+        d_line_len = static_cast<uint32_t*>(alloc(ns * 4));
+        d_wakati_tiles = static_cast<uint64_t*>(alloc(((ns + kScanTile - 1) / kScanTile + 1) * 8));
+        d_line_off = static_cast<uint64_t*>(alloc((ns + 1) * 8));
+        d_wakati = static_cast<uint8_t*>(alloc(((cap + 3) & ~3ull) + kWakatiPad));
+    }
+    wakati = on;
+    wakati_keep = on && keep_records;
+    if (on) {
+        const uint64_t cap = 2 * max_bytes + std::max<uint64_t>(max_sentences, 1);
+        wakati_cap = cap_limit ? std::min(cap, cap_limit) : cap;
+    }
 }
 
 void Workspace::pack_to(vbt_token_rec* out_tokens, uint32_t* out_off, uint32_t* out_cnt, void* stream_) {

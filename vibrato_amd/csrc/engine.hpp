@@ -120,7 +120,8 @@ constexpr int kProfSlots = 256;  // the counters are spread over this many copie
 constexpr int kProfWords = 12;   // kProfPhases cycle totals, sentences, lattice steps, lattice passes, candidates
 constexpr int kProfPhases = 8;  // decode, count, fill, end lists, pre-pass, gather, recurrence, emit
 // kErrOffsets / kErrUtf8 are set by validate_batch; the batch is then skipped (no kernel touches the per-sentence regions)
-enum DevError { kErrTokCap = 1, kErrScratch = 2, kErrTooLong = 4, kErrOffsets = 8, kErrUtf8 = 16, kErrFatal = kErrOffsets | kErrUtf8 };
+// kErrWakatiCap: a line of the wakati output would have ended beyond the output buffer (wakati_render; the line is not written)
+enum DevError { kErrTokCap = 1, kErrScratch = 2, kErrTooLong = 4, kErrOffsets = 8, kErrUtf8 = 16, kErrWakatiCap = 32, kErrFatal = kErrOffsets | kErrUtf8 };
 
 // What a kernel launch reads of the dictionary.  The connection ids inside it -- the rows and columns of the matrix, the id pairs of
 // the entry arrays -- are DEVICE ids: image 0 numbers them as the dictionary does; the image a tokenizer builds from the usage
@@ -222,6 +223,18 @@ class Workspace {
     // max_sentences] [24-byte token records] -- tok_cnt by the sweep, tok_off and the records by compact_tokens, the header with its
     // total: no copy kernels between the tokenizer and the collective.  slot == nullptr: back to the workspace's own buffers.
     void set_packed_output(void* slot, uint64_t slot_bytes, uint64_t max_sentences);
+    // Wakati output mode (wakati.hip): every later run() also leaves the segmented text of the batch -- line s = the surfaces of
+    // sentence s joined by ' ' + '\n', lines back to back -- in d_wakati and the lines' byte offsets in d_line_off[n + 1]
+    // (d_line_off[n] = bytes written), rendered from the staging regions behind the sweeps; the token records are packed only
+    // when keep_records is set.  The buffers are allocated when the mode is first switched on, for the largest batch the workspace
+    // takes: max_bytes of text + as many tokens + a byte per sentence.  cap_limit > 0: the kernels may use that many bytes of the
+    // buffer only (a line that would end beyond them sets kErrWakatiCap and is not written).
+    void set_wakati(bool on, bool keep_records, uint64_t cap_limit = 0);
+    bool wakati = false, wakati_keep = false;
+    uint8_t* d_wakati = nullptr;
+    uint64_t* d_line_off = nullptr;
+    uint64_t wakati_cap = 0;
+    static constexpr uint64_t kWakatiPad = 64;  // bytes behind the capacity that are allocated and never written
     void* packed_slot = nullptr;
     uint64_t packed_bytes = 0, packed_max_s = 0;
     void stats(vbt_call_stats* out);  // synchronizes the last stream used
@@ -271,6 +284,8 @@ class Workspace {
     void* last_stream = nullptr;
     bool has_run = false;  // (last_stream == nullptr is the null stream, not "never ran")
     void* ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t* d_line_len = nullptr;      // wakati mode: bytes per line, bytes per tile of kScanTile lines
+    uint64_t* d_wakati_tiles = nullptr;
 
   private:
     void release();  // frees every device allocation, stream and event (also on a constructor failure)

@@ -1,4 +1,4 @@
-// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip), as plain
+// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip, wakati.hip), as plain
 // functions the host side (engine.hip: Tokenizer, Workspace) calls.  Every launcher enqueues on `stream` and returns.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -53,6 +53,14 @@ void expand_connector_i16(dim3 grid, const DevConnector& c, int16_t* out, uint32
 void expand_connector_i32(dim3 grid, const DevConnector& c, int32_t* out, uint32_t num_right, uint32_t num_left, uint32_t* range_flag);
 // dst[l][r] = src[inv_left[l]][inv_right[r]] (i16 cells, or i32 when `wide`): the matrix under a renumbering of the connection ids
 void permute_matrix(hipStream_t stream, const void* src, void* dst, bool wide, const uint16_t* inv_left, const uint16_t* inv_right, uint32_t num_left, uint32_t num_right);
+
+// ---- wakati.hip: the segmented text of a batch ("surface surface ...\n" per sentence, back to back) from the staging regions
+// wakati_plan (line_len[n], bytes per tile) -> wakati_scan (tile_bytes[] -> exclusive prefix, line_off[n] = total; count_tokens: also
+// ctrl[kTotal] from tile_sums[], for a batch whose records are not packed) -> wakati_render (line_off[0 .. n), the lines into out;
+// a line that would end beyond out_cap sets kErrWakatiCap and is not written).  tile_bytes: n_tiles words, n_tiles = ceil(n / kScanTile).
+uint32_t wakati_round();  // tokens per LDS round of wakati_render
+void wakati_lines(hipStream_t stream, const BatchArgs& a, uint32_t n_tiles, uint32_t* line_len, uint64_t* tile_bytes, uint64_t* line_off, uint8_t* out,
+                  uint64_t out_cap, bool count_tokens);
 
 // the calibration sample (Tokenizer::maybe_calibrate): up to `want` sentences spread evenly over the batch, copied into s_text / s_offs
 // (s_offs[0 .. k], k = info[0] = the sentences whose text fits cap_bytes; s_src: want words of scratch), on `stream`

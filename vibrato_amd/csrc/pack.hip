@@ -12,18 +12,6 @@ namespace {
 // of more than 2048 tiles and for callers that pack later.)
 constexpr uint32_t kScanItems = 1;
 static_assert(kScanTile == kScanBlock * kScanItems, "one sentence per thread of a packing workgroup");
-__device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t* warp_sums, uint32_t& block_total) {
-    uint32_t wtot;
-    const uint32_t ex = wave_exscan_any(v, wtot);
-    const uint32_t w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if ((threadIdx.x & 63u) == 0) warp_sums[w] = wtot;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-    for (uint32_t i = 0; i < nw; ++i) { const uint32_t t = warp_sums[i]; if (i < w) base += t; tot += t; }
-    __syncthreads();
-    block_total = tot;
-    return base + ex;
-}
 // Header of a packed result slot (Workspace::set_packed_output): {n_sentences u64, n_tokens u32, error flags u32, 0 x 4}.  A slot that
 // is too small for this batch reports the records it holds (never more than were written) and says so in the flags word -- a consumer
 // of the gathered slots on another rank sees nothing else of this rank's state (round-5 advisor).
