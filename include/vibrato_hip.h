@@ -272,6 +272,19 @@ VBT_API void vbt_free(void* p);
  * one device) is refused with VBT_ERR_UNSUPPORTED: sharded rendering is not implemented. */
 VBT_API int vbt_tokenize_wakati(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
                                 char** out, size_t* len, uint64_t* line_off);
+/* Host text in -> MeCab-format text out (tokenize/src/main.rs:83-95: "surface \t feature \n" per token, then "EOS\n"; "EOS\n" alone
+ * for a sentence without tokens; the lines of the n sentences back to back), rendered ON THE DEVICE: the same bytes as
+ * vbt_tokenize_batch + vbt_batch_format(VBT_FORMAT_MECAB), but no token records are packed or copied and no host thread formats
+ * anything -- the feature strings are a table of the device image (uploaded at the first call), kernels behind the sweeps write the
+ * lines (vbt_workspace_set_mecab), 16 bytes come back and exactly *len bytes are copied into a pinned block by the SDMA engine.
+ * The input does not bound this output: the first capacity is taken from the largest output-per-input ratio this tokenizer has seen
+ * (+ 1/8 + 4 n; 8 x bytes + 4 n before any batch; VBT_MECAB_FIRST_CAP = bytes in the environment, read per call, overrides it), and
+ * a batch that does not fit is rendered ONCE more into a buffer of the exact size (vbt_workspace_render_again), not tokenized again.
+ * *out is released ONLY with vbt_free; line_off (optional): n + 1 entries, line_off[n] = *len.  Input contract and error codes as
+ * vbt_tokenize_batch.  One unpipelined call on a pooled workspace; thread-safe per tokenizer.  A multi-device tokenizer is refused
+ * with VBT_ERR_UNSUPPORTED: sharded rendering is not implemented. */
+VBT_API int vbt_tokenize_mecab(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
+                               char** out, size_t* len, uint64_t* line_off);
 
 /* ---- Device-resident API (zero-copy; what bench.py times) ------------------------ */
 
@@ -326,15 +339,33 @@ VBT_API int vbt_workspace_set_packed_output(vbt_workspace* ws, void* d_slot, uin
 #define VBT_WAKATI_ROUND 256
 VBT_API int vbt_workspace_set_wakati(vbt_workspace* ws, int enabled, int keep_records);
 VBT_API int vbt_workspace_wakati(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off /* n + 1 */);
+/* MeCab-format output on the device (tokenize/src/main.rs:83-95).  While enabled, every vbt_tokenize_batch_device call of this
+ * workspace also renders the MeCab-format text of its batch -- per token "surface \t feature \n", per sentence "EOS\n" -- straight
+ * from the sweeps' per-sentence staging and the feature table of the device image (uploaded when the first workspace of a tokenizer
+ * enables the mode); the token records are NOT packed unless keep_records is set.  One text mode at a time: enabling this mode on a
+ * workspace in wakati mode, or the reverse, is VBT_ERR_INVALID_ARGUMENT.  A wave renders a sentence VBT_MECAB_ROUND tokens at a time.
+ * cap_bytes (> 0 when enabling): the capacity of the output buffer, which the input does NOT bound (a token adds its feature string,
+ * 40-150 bytes with the usual dictionaries).  The buffer is allocated, or replaced by a larger one, when more is asked for than it
+ * holds.  A line that would end beyond the capacity (or a line of 4 GiB and more) sets error flag 32 -- the text output capacity flag
+ * of both text modes -- and is not written, the lines in front of it are; d_line_off[n] is the exact number of bytes the batch needs
+ * either way.  The 64 bytes behind the capacity belong to the buffer and are never written.
+ * vbt_workspace_mecab: as vbt_workspace_wakati (the pointer changes when the buffer is replaced).
+ * vbt_workspace_render_again (tokenize/src/main.rs:83-95): valid after a call in this mode until the next one, the batch's d_text /
+ * d_offsets still in place: takes flag 32 back on `hip_stream` and renders the lines once more -- after vbt_workspace_set_mecab with
+ * a larger cap_bytes, growing the buffer costs one render kernel, not a second tokenization. */
+#define VBT_MECAB_ROUND 128
+VBT_API int vbt_workspace_set_mecab(vbt_workspace* ws, int enabled, int keep_records, uint64_t cap_bytes);
+VBT_API int vbt_workspace_mecab(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off /* n + 1 */);
+VBT_API int vbt_workspace_render_again(vbt_workspace* ws, void* hip_stream);
 /* Per-call statistics (synchronizes the stream of the last call): how many sentences were filed
  * in the LDS tiers sentences are routed to up front -- the lean tier and the segment tier (n_tier0) --, in the escape tiers behind
  * them (n_tier1: what a sweep passed on) and in the list of the global-memory fallback kernel (n_tier2; a re-routed sentence is
  * counted in every list it was filed in), tokens
  * written, device error flags (1 = token buffer full, 2 = scratch exhausted, 4 = sentence too
- * long, 8 = bad offsets, 16 = invalid UTF-8, 32 = a wakati line did not fit the output buffer) and, with timing enabled, the hipEvent-measured durations (ms, on the launch stream) of the
+ * long, 8 = bad offsets, 16 = invalid UTF-8, 32 = a line of the text output -- wakati or MeCab mode -- did not fit the output buffer) and, with timing enabled, the hipEvent-measured durations (ms, on the launch stream) of the
  * input check and the candidate generators (ms_tier0: validate_batch, gen_candidates, build_lists, the gen_long levels), of the
  * lattice sweeps from their fork to their join (ms_tier12) and of what follows -- the global-memory fallback launch and the packing
- * of the token records and, in wakati mode, the three kernels that render the lines (ms_pack). */
+ * of the token records and, in wakati or MeCab mode, the three kernels that render the lines (ms_pack). */
 typedef struct vbt_call_stats {
     uint64_t n_sentences, n_tier0, n_tier1, n_tier2, n_tokens;
     uint32_t error_flags;

@@ -149,15 +149,30 @@ impl Tokenizer {
     /// rendered on the device (new): the bytes of `tokenize_batch(..)?.format(OutputMode::Wakati)` without token records or host
     /// formatter threads. Returns the text and the `n + 1` byte offsets of its lines. Single-device tokenizers only.
     pub fn tokenize_wakati_raw(&self, text: &[u8], offsets: &[u64]) -> Result<(String, Vec<u64>)> {
+        self.tokenize_text_raw(sys::vbt_tokenize_wakati, text, offsets)
+    }
+
+    /// MeCab-format output of many sentences (`tokenize/src/main.rs:83-95`: `surface \t feature \n` per token, `EOS\n` per
+    /// sentence), rendered on the device (new): the bytes of `tokenize_batch(..)?.format(OutputMode::Mecab)` without token records
+    /// or host formatter threads. Returns as `tokenize_wakati_raw` does. Single-device tokenizers only.
+    pub fn tokenize_mecab_raw(&self, text: &[u8], offsets: &[u64]) -> Result<(String, Vec<u64>)> {
+        self.tokenize_text_raw(sys::vbt_tokenize_mecab, text, offsets)
+    }
+
+    fn tokenize_text_raw(
+        &self,
+        call: unsafe extern "C" fn(*const sys::vbt_tokenizer, *const u8, *const u64, u64, *mut *mut std::os::raw::c_char, *mut usize, *mut u64) -> std::os::raw::c_int,
+        text: &[u8],
+        offsets: &[u64],
+    ) -> Result<(String, Vec<u64>)> {
         if offsets.is_empty() || *offsets.last().unwrap() as usize > text.len() {
             return Err(VibratoError::invalid_argument("offsets", "offsets must hold n + 1 positions inside text"));
         }
         let (mut p, mut n): (*mut std::os::raw::c_char, usize) = (ptr::null_mut(), 0);
         let mut line_off = vec![0u64; offsets.len()];
-        check(unsafe {
-            sys::vbt_tokenize_wakati(self.raw()?, text.as_ptr(), offsets.as_ptr(), (offsets.len() - 1) as u64, &mut p, &mut n, line_off.as_mut_ptr())
-        })?;
-        // Safety: the surfaces are slices of validated UTF-8 cut at character boundaries, the separators ASCII
+        check(unsafe { call(self.raw()?, text.as_ptr(), offsets.as_ptr(), (offsets.len() - 1) as u64, &mut p, &mut n, line_off.as_mut_ptr()) })?;
+        // Safety: surfaces are slices of validated UTF-8 cut at character boundaries, features are dictionary strings (UTF-8 by
+        // construction), the separators ASCII
         let s = unsafe { std::str::from_utf8_unchecked(std::slice::from_raw_parts(p as *const u8, n)) }.to_owned();
         unsafe { sys::vbt_free(p as *mut _) };
         Ok((s, line_off))

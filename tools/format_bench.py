@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer aid: vbt_batch_format call by call on one headline-sized batch (cold / warm buffer, thread counts).
 usage (GPU box): python tools/format_bench.py [threads ...]
-                 python tools/format_bench.py --wakati    (wakati text: host formatter route against the device route)"""
+                 python tools/format_bench.py --wakati    (wakati text: host formatter route against the device route)
+                 python tools/format_bench.py --mecab     (MeCab-format text: the same two routes)"""
 import ctypes as C
 import os
 import subprocess
@@ -33,11 +34,12 @@ def one():
           + f"; best {n.value / min(ts) / 1e6:.1f} GB/s")
 
 
-def wakati(rounds=12, calls=8):
-    """Text in -> wakati text out on one headline-sized batch, one caller thread, one process: the host route (vbt_tokenize_batch +
-    vbt_batch_format + the frees) against the device route (vbt_tokenize_wakati + vbt_free), alternating, `calls` calls per timed
-    window; medians, the run-to-run spread of either route, the bytes that leave the device per batch, and ms_pack of the
-    device-resident call (the fallback launch + the record packing, or + the three wakati kernels) with and without wakati mode."""
+def routes(mode, rounds=12, calls=8):
+    """Text in -> wakati / MeCab-format text out on one headline-sized batch, one caller thread, one process: the host route
+    (vbt_tokenize_batch + vbt_batch_format + the frees) against the device route (vbt_tokenize_wakati / vbt_tokenize_mecab + vbt_free),
+    alternating, `calls` calls per timed window; medians, the run-to-run spread of either route, the bytes that leave the device per
+    batch, and ms_pack of the device-resident call (the fallback launch + the record packing, or + the three kernels of the text
+    mode) with and without the text mode."""
     import statistics
     import numpy as np
     import torch
@@ -53,7 +55,7 @@ def wakati(rounds=12, calls=8):
     def host():
         b, p, ln = C.c_void_p(), C.c_void_p(), C.c_size_t()
         N.check(L.vbt_tokenize_batch(h, text.ctypes.data, offs.ctypes.data, n, C.byref(b)))
-        N.check(L.vbt_batch_format(b, 1, C.byref(p), C.byref(ln)))
+        N.check(L.vbt_batch_format(b, 1 if mode == "wakati" else 0, C.byref(p), C.byref(ln)))
         nt = L.vbt_batch_total_tokens(b)
         L.vbt_free(p)
         L.vbt_batch_free(b)
@@ -61,12 +63,12 @@ def wakati(rounds=12, calls=8):
 
     def device():
         p, ln = C.c_void_p(), C.c_size_t()
-        N.check(L.vbt_tokenize_wakati(h, text.ctypes.data, offs.ctypes.data, n, C.byref(p), C.byref(ln), None))
+        N.check(getattr(L, "vbt_tokenize_" + mode)(h, text.ctypes.data, offs.ctypes.data, n, C.byref(p), C.byref(ln), None))
         L.vbt_free(p)
         return ln.value, ln.value
 
-    ref = tok.tokenize_batch(text=text, offsets=offs).format("wakati").encode()
-    assert tok.tokenize_wakati(text=text, offsets=offs) == ref  # (the same bytes at the size that is timed)
+    ref = tok.tokenize_batch(text=text, offsets=offs).format(mode).encode()
+    assert getattr(tok, "tokenize_" + mode)(text=text, offsets=offs) == ref  # (the same bytes at the size that is timed)
     for _ in range(3):  # warm-up: pools, pinned blocks, the renumbered image
         host(), device()
     tok.wait_connid_reorder()
@@ -86,18 +88,21 @@ def wakati(rounds=12, calls=8):
     d_text, d_offs = torch.from_numpy(text).cuda(), torch.from_numpy(offs.astype(np.int64)).cuda()
     ws = tok.workspace(n, len(text))
     ws.set_timing(True)
-    for mode in (False, True):
-        ws.set_wakati(mode)
+    for on in (False, True):
+        if mode == "wakati":
+            ws.set_wakati(on)
+        else:
+            ws.set_mecab(on, cap_bytes=len(ref))
         v = []
         for _ in range(10):
             ws.run(d_text.data_ptr(), d_offs.data_ptr(), n, len(text), torch.cuda.current_stream().cuda_stream)
             v.append(ws.stats()["ms_pack"])
-        print(f"ms_pack, device-resident call, wakati mode {'on (records not packed)' if mode else 'off'}: median {statistics.median(v[2:]):.4f} ms")
+        print(f"ms_pack, device-resident call, {mode} mode {'on (records not packed)' if on else 'off'}: median {statistics.median(v[2:]):.4f} ms")
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--wakati":
-        wakati()
+    if len(sys.argv) > 1 and sys.argv[1] in ("--wakati", "--mecab"):
+        routes(sys.argv[1][2:])
     elif len(sys.argv) > 1 and sys.argv[1] == "--one":
         one()
     else:

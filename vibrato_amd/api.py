@@ -334,6 +334,15 @@ class Tokenizer:
         """Host text in -> wakati text out (tokenize/src/main.rs:96-103), rendered on the device (vbt_tokenize_wakati): the bytes of
         tokenize_batch(...).format("wakati") without token records or host formatter threads.  Returns bytes, or with
         `with_offsets` (bytes, np.uint64[n + 1]): line s is out[line_off[s]:line_off[s + 1]].  Single-device tokenizers only."""
+        return self._tokenize_text(N.lib().vbt_tokenize_wakati, sentences, text, offsets, with_offsets)
+
+    def tokenize_mecab(self, sentences=None, text=None, offsets=None, with_offsets=False):
+        """Host text in -> MeCab-format text out (tokenize/src/main.rs:83-95: "surface\\tfeature\\n" per token, "EOS\\n" per sentence),
+        rendered on the device (vbt_tokenize_mecab): the bytes of tokenize_batch(...).format("mecab") without token records or
+        host formatter threads.  Returns as tokenize_wakati does.  Single-device tokenizers only."""
+        return self._tokenize_text(N.lib().vbt_tokenize_mecab, sentences, text, offsets, with_offsets)
+
+    def _tokenize_text(self, call, sentences, text, offsets, with_offsets):
         if sentences is not None:
             enc = [_b(s) for s in sentences]
             offsets = np.zeros(len(enc) + 1, dtype=np.uint64)
@@ -345,8 +354,8 @@ class Tokenizer:
         n = len(offsets) - 1
         line_off = np.zeros(n + 1, dtype=np.uint64) if with_offsets else None
         p, ln = C.c_void_p(), C.c_size_t()
-        N.check(N.lib().vbt_tokenize_wakati(self._handle(), text.ctypes.data if text.size else None, offsets.ctypes.data, n, C.byref(p), C.byref(ln),
-                                            line_off.ctypes.data if with_offsets else None))
+        N.check(call(self._handle(), text.ctypes.data if text.size else None, offsets.ctypes.data, n, C.byref(p), C.byref(ln),
+                     line_off.ctypes.data if with_offsets else None))
         try:
             out = C.string_at(p, ln.value)
         finally:
@@ -710,6 +719,24 @@ class Workspace:
         o, lo = C.c_void_p(), C.c_void_p()
         N.check(N.lib().vbt_workspace_wakati(self._h, C.byref(o), C.byref(lo)))
         return {"out": o.value, "line_off": lo.value}
+
+    def set_mecab(self, on=True, keep_records=False, cap_bytes=0):
+        """Every later run() also renders the batch's MeCab-format text on the device (mecab_ptrs); the token records are packed
+        only with keep_records.  cap_bytes (> 0 when enabling): the capacity of the output buffer, which the input does not bound;
+        a line that would end beyond it sets error flag 32 and is not written, line_off[n] is the exact need either way.  Not
+        while wakati mode is on."""
+        N.check(N.lib().vbt_workspace_set_mecab(self._h, int(bool(on)), int(keep_records), int(cap_bytes)))
+
+    def mecab_ptrs(self):
+        """Device addresses {"out": the lines back to back, "line_off": u64[n + 1], line_off[n] = bytes the batch needs} of the last run()."""
+        o, lo = C.c_void_p(), C.c_void_p()
+        N.check(N.lib().vbt_workspace_mecab(self._h, C.byref(o), C.byref(lo)))
+        return {"out": o.value, "line_off": lo.value}
+
+    def render_again(self, stream):
+        """After a run() in MeCab mode, before the next one: clears error flag 32 and renders the lines once more on `stream` --
+        with a larger set_mecab(cap_bytes=...) in between, growing the buffer costs one render, not a second tokenisation."""
+        N.check(N.lib().vbt_workspace_render_again(self._h, stream or None))
 
     def result_ptrs(self):
         p = [C.c_void_p() for _ in range(4)]

@@ -54,10 +54,12 @@ def main(argv=None, stdin=None, stdout=None):
     # Three stages, each on its own thread (the library calls release the GIL): this thread reads lines and cuts blocks, one thread
     # pushes block k + 1 through the GPU (vbt_tokenize_batch), one renders block k (vbt_batch_format) and writes it -- the formatter
     # of one block runs under the kernels and copies of the next.  Output order = input order (one block at a time per stage).
-    # (-O wakati: the block's text is rendered on the device -- Tokenizer.tokenize_wakati -- and the output stage only writes it)
+    # (-O wakati and -O mecab: the block's text is rendered on the device -- Tokenizer.tokenize_wakati / tokenize_mecab -- and the
+    # output stage only writes it)
     import queue
     import threading
-    wakati_on_device = args.output_mode == "wakati" and tok.num_devices() == 1
+    text_on_device = args.output_mode in ("wakati", "mecab") and tok.num_devices() == 1
+    tokenize_text = tok.tokenize_wakati if args.output_mode == "wakati" else tok.tokenize_mecab
     blocks, batches = queue.Queue(maxsize=2), queue.Queue(maxsize=2)
     failure = []
 
@@ -68,7 +70,7 @@ def main(argv=None, stdin=None, stdout=None):
                 if lines is None:
                     break
                 if not failure:
-                    batches.put(tok.tokenize_wakati(lines) if wakati_on_device else tok.tokenize_batch(lines))
+                    batches.put(tokenize_text(lines) if text_on_device else tok.tokenize_batch(lines))
         except BaseException as e:  # noqa: BLE001 -- reported by the main thread
             failure.append(e)
             while blocks.get() is not None:  # (keep draining: the reader must not block on a full queue)
@@ -82,7 +84,7 @@ def main(argv=None, stdin=None, stdout=None):
                 if b is None:
                     break
                 if not failure:
-                    if wakati_on_device:
+                    if text_on_device:
                         stdout.write(b)
                     else:
                         b.format_into(stdout.write, args.output_mode)

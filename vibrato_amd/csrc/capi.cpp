@@ -229,12 +229,11 @@ struct vbt_tokenizer {
     std::mutex pool_mu;
     std::vector<std::unique_ptr<PinnedBlock>> host_pool;  // idle pinned blocks
     uint64_t pool_created = 0, pool_reused = 0;
-    // feature strings of the three lexicons (system, user, unknown) back to back + offsets per word id: what vbt_batch_format reads
-    // instead of 877 k separately allocated std::strings (built at the first format call)
-    struct FlatFeatures { std::vector<uint32_t> off; std::vector<char> blob; } flat[3];
-    std::once_flag flat_once;
+    // (the flat feature strings vbt_batch_format reads live in the engine's Tokenizer: flat_features(), shared with the device table)
     // tokens per KiB of text the batches so far produced at most (0: none yet): sizes the result block of a pipelined call up front
     std::atomic<uint32_t> tok_per_kib{0};
+    // bytes of MeCab-format output per KiB of text, likewise: the first capacity of vbt_tokenize_mecab
+    std::atomic<uint32_t> mecab_per_kib{0};
     // vbt_tokenize_batch calls running right now, calls started so far, and the last call that saw another one in flight: only a
     // caller that has been alone for a while gets its batch pipelined in chunks (host threads that stream batches side by side
     // overlap each other's copies and kernels already; a chunked call in their midst is slower for everybody)
@@ -342,7 +341,7 @@ void check_device_errors(uint32_t flags) {
     if (flags & kErrTokCap) throw Error(VBT_ERR_INVALID_STATE, "device token buffer overflow");
     if (flags & kErrScratch) throw Error(VBT_ERR_UNSUPPORTED, "device scratch arena exhausted (raise VBT_SCRATCH_MB)");
     if (flags & kErrTooLong) throw Error(VBT_ERR_UNSUPPORTED, "sentence too long for the device image (>= 4 GiB or >= 2^32 lattice nodes)");
-    if (flags & kErrWakatiCap) throw Error(VBT_ERR_INVALID_STATE, "device wakati buffer overflow");
+    if (flags & kErrWakatiCap) throw Error(VBT_ERR_INVALID_STATE, "device text output buffer overflow (wakati or MeCab mode)");
 }
 
 // Token accessors (token.rs:21-92) from a raw record.
@@ -1496,11 +1495,17 @@ int vbt_tokenize_batch(const vbt_tokenizer* tok_, const uint8_t* text, const uin
 // Text in -> wakati text out, rendered on the device (wakati.hip).  One unpipelined call: the text and its offsets go in, the
 // launch sequence of the batch ends with the wakati kernels instead of the record packing, 16 bytes come back ({tokens, error
 // flags}, the output's length), then exactly that many bytes and line_off[] leave the device on the copy engine.
-int vbt_tokenize_wakati(const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len, uint64_t* line_off) {
+// MeCab format (mecab.hip) likewise, plus the capacity protocol: the input does not bound that output, so the call names a first
+// capacity -- from the largest output-per-input ratio the tokenizer has seen -- and a batch that does not fit (error flag 32 alone)
+// is rendered once more into a buffer of the exact size the device reported (Workspace::render_text_again), not tokenized again.
+static int tokenize_text_on_device(bool mecab, const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len,
+                                   uint64_t* line_off) {
     return guarded([&] {
         vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
         if (!tok || !offsets || !out || !len || (!text && n && offsets[n] != offsets[0])) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
-        if (tok->reps.size() > 1) throw Error(VBT_ERR_UNSUPPORTED, "vbt_tokenize_wakati: a multi-device tokenizer cannot render wakati output (sharded rendering is not implemented)");
+        if (tok->reps.size() > 1)
+            throw Error(VBT_ERR_UNSUPPORTED, mecab ? "vbt_tokenize_mecab: a multi-device tokenizer cannot render MeCab output (sharded rendering is not implemented)"
+                                                   : "vbt_tokenize_wakati: a multi-device tokenizer cannot render wakati output (sharded rendering is not implemented)");
         const uint64_t lo = offsets[0];
         for (uint64_t i = 1; i <= n; ++i)
             if (offsets[i] < offsets[i - 1]) throw Error(VBT_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
@@ -1526,6 +1531,7 @@ int vbt_tokenize_wakati(const vbt_tokenizer* tok_, const uint8_t* text, const ui
                     (void)hipSetDevice(rep.t->device());
                     (void)hipStreamSynchronize(p->stream);
                     p->ws->set_wakati(false, false);
+                    p->ws->set_mecab(false, false, 0);
                     pool_give(tok, rep, std::move(p));
                 }
                 host_give(tok, std::move(blk));
@@ -1546,7 +1552,16 @@ int vbt_tokenize_wakati(const vbt_tokenizer* tok_, const uint8_t* text, const ui
         HIPX(hipSetDevice(rep.t->device()));
         h.p = pool_take(tok, rep, n, bytes);
         PooledWorkspace& p = *h.p;
-        p.ws->set_wakati(true, false);
+        if (mecab) {
+            // first capacity: the running maximum of output bytes per KiB of input + 1/8 + "EOS\n" per sentence; 8 x the input before
+            // any batch has been seen; VBT_MECAB_FIRST_CAP (bytes, read per call: tests, A/B runs) overrides
+            const uint32_t r = tok->mecab_per_kib.load(std::memory_order_relaxed);
+            uint64_t cap = (r ? (bytes * r / 1024) * 9 / 8 : 8 * bytes) + 4 * n;
+            if (const char* e = std::getenv("VBT_MECAB_FIRST_CAP")) { const uint64_t v = std::strtoull(e, nullptr, 10); if (v) cap = v; }
+            p.ws->set_mecab(true, false, cap);
+        } else {
+            p.ws->set_wakati(true, false);
+        }
         if (bytes) HIPX(hipMemcpyAsync(p.d_text, txt, bytes, hipMemcpyHostToDevice, p.stream));
         HIPX(hipMemcpyAsync(p.d_off, offs, (n + 1) * 8, hipMemcpyHostToDevice, p.stream));
         p.ws->run(static_cast<const uint8_t*>(p.d_text), p.d_off, n, bytes, p.stream);
@@ -1557,17 +1572,29 @@ int vbt_tokenize_wakati(const vbt_tokenizer* tok_, const uint8_t* text, const ui
             for (uint64_t i = 0; i < n; ++i)
                 if (!valid_utf8(txt + offs[i], offs[i + 1] - offs[i])) throw Error(VBT_ERR_UTF8, "sentence " + std::to_string(i) + " is not valid UTF-8");
         }
+        if (mecab && tail[1] == (uint32_t)kErrWakatiCap) {  // the capacity alone: the exact need is known now -- grow, render once more
+            p.ws->set_mecab(true, false, *total);
+            p.ws->render_text_again(p.stream);
+            HIPX(hipMemcpyAsync(tail, p.ws->d_ctrl, 8, hipMemcpyDeviceToHost, p.stream));
+            HIPX(hipStreamSynchronize(p.stream));
+            if (tail[1] & kErrWakatiCap) throw Error(VBT_ERR_DEVICE, "vbt_tokenize_mecab: the text does not fit a buffer of the size the device asked for");
+        }
         check_device_errors(tail[1]);
         const size_t out_bytes = (size_t)*total;
+        if (mecab && bytes) {  // bytes of output per KiB of text, rounded up: the largest seen
+            const uint32_t r = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, ((uint64_t)out_bytes * 1024 + bytes - 1) / bytes + 1);
+            uint32_t cur = tok->mecab_per_kib.load(std::memory_order_relaxed);
+            while (r > cur && !tok->mecab_per_kib.compare_exchange_weak(cur, r, std::memory_order_relaxed)) {}
+        }
         h.result = pin_out_alloc(out_bytes);
-        const void* src[2] = {p.ws->d_wakati, p.ws->d_line_off};
+        const void* src[2] = {mecab ? p.ws->d_mecab : p.ws->d_wakati, p.ws->d_line_off};
         void* dst[2] = {h.result, loff};
         const size_t sz[2] = {out_bytes, line_off ? (size_t)(n + 1) * 8 : 0};
         if (use_sdma) {
             std::vector<hsa_signal_t> sigs;
             bool ok = rep.sdma->issue(src, dst, sz, 2, sigs);
             ok = Sdma::wait(sigs) && ok;
-            if (!ok) throw Error(VBT_ERR_DEVICE, "device -> host copy of the wakati text failed (hsa_amd_memory_async_copy)");
+            if (!ok) throw Error(VBT_ERR_DEVICE, "device -> host copy of the rendered text failed (hsa_amd_memory_async_copy)");
         } else {
             for (int k = 0; k < 2; ++k)
                 if (sz[k]) HIPX(hipMemcpyAsync(dst[k], src[k], sz[k], hipMemcpyDeviceToHost, p.stream));
@@ -1577,6 +1604,14 @@ int vbt_tokenize_wakati(const vbt_tokenizer* tok_, const uint8_t* text, const ui
         *out = static_cast<char*>(h.result); *len = out_bytes;
         h.result = nullptr;
     });
+}
+
+int vbt_tokenize_wakati(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len, uint64_t* line_off) {
+    return tokenize_text_on_device(false, tok, text, offsets, n, out, len, line_off);
+}
+
+int vbt_tokenize_mecab(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len, uint64_t* line_off) {
+    return tokenize_text_on_device(true, tok, text, offsets, n, out, len, line_off);
 }
 
 // Releases every idle pooled workspace and pinned block now (they are re-created on demand).
@@ -1690,23 +1725,8 @@ int vbt_batch_format(const vbt_batch* b, int mode, char** out, size_t* len) {
         const uint64_t n = b->n;
         // The feature strings, flat: one blob per lexicon + a u32 offset per word id (3.5 MB of offsets for unidic: they stay in the
         // host's caches, where 877 k separately allocated std::strings cost a cache miss per token for the length alone).
-        vbt_tokenizer* tk = b->tok;
-        std::call_once(tk->flat_once, [&] {
-            auto flatten = [](const std::vector<std::string>& f, vbt_tokenizer::FlatFeatures& o) {
-                size_t total = 0;
-                for (const auto& x : f) total += x.size();
-                if (total >= 0xFFFFFFFFull) throw Error(VBT_ERR_UNSUPPORTED, "format: more than 4 GiB of feature strings");
-                o.off.resize(f.size() + 1);
-                o.blob.resize(total);
-                size_t at = 0;
-                for (size_t i = 0; i < f.size(); ++i) { o.off[i] = (uint32_t)at; std::memcpy(o.blob.data() + at, f[i].data(), f[i].size()); at += f[i].size(); }
-                o.off[f.size()] = (uint32_t)at;
-            };
-            flatten(d.system.features, tk->flat[VBT_LEX_SYSTEM]);
-            if (d.has_user) flatten(d.user.features, tk->flat[VBT_LEX_USER]); else tk->flat[VBT_LEX_USER].off.assign(1, 0);
-            flatten(d.unk_features, tk->flat[VBT_LEX_UNKNOWN]);
-        });
-        const vbt_tokenizer::FlatFeatures* flat = tk->flat;
+        // (Tokenizer::flat_features: built at the first call, also the source of the device's feature table)
+        const FlatFeatures* flat = b->tok->t->flat_features();
         // chunks of sentences balanced by tokens (tok_off is non-decreasing in sentence order)
         unsigned want = std::thread::hardware_concurrency();
         if (want == 0) want = 1;
@@ -1874,6 +1894,29 @@ int vbt_workspace_wakati(const vbt_workspace* ws, const uint8_t** d_out, const u
         if (!ws->w->d_wakati) throw Error(VBT_ERR_INVALID_STATE, "wakati output was never enabled on this workspace (vbt_workspace_set_wakati)");
         if (d_out) *d_out = ws->w->d_wakati;
         if (d_line_off) *d_line_off = ws->w->d_line_off;
+    });
+}
+
+int vbt_workspace_set_mecab(vbt_workspace* ws, int enabled, int keep_records, uint64_t cap_bytes) {
+    return guarded([&] {
+        if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null workspace");
+        ws->w->set_mecab(enabled != 0, keep_records != 0, cap_bytes);
+    });
+}
+
+int vbt_workspace_mecab(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off) {
+    return guarded([&] {
+        if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (!ws->w->d_mecab) throw Error(VBT_ERR_INVALID_STATE, "MeCab output was never enabled on this workspace (vbt_workspace_set_mecab)");
+        if (d_out) *d_out = ws->w->d_mecab;
+        if (d_line_off) *d_line_off = ws->w->d_line_off;
+    });
+}
+
+int vbt_workspace_render_again(vbt_workspace* ws, void* hip_stream) {
+    return guarded([&] {
+        if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null workspace");
+        ws->w->render_text_again(hip_stream);
     });
 }
 

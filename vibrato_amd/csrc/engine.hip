@@ -240,7 +240,72 @@ Tokenizer::~Tokenizer() {
     for (auto& im : images_)
         for (void* p : im->allocs) (void)hipFree(p);
     for (void* p : allocs_) (void)hipFree(p);
+    for (void* p : feat_allocs_) if (p) (void)hipFree(p);
     if (density_host_) (void)hipHostFree(density_host_);
+}
+
+const FlatFeatures* Tokenizer::flat_features() const {
+    std::call_once(flat_once_, [&] {
+        auto flatten = [](const std::vector<std::string>& f, FlatFeatures& o) {
+            size_t total = 0;
+            for (const auto& x : f) total += x.size();
+            if (total >= 0xFFFFFFFFull) throw Error(VBT_ERR_UNSUPPORTED, "format: more than 4 GiB of feature strings");
+            o.off.resize(f.size() + 1);
+            o.blob.resize(total);
+            size_t at = 0;
+            for (size_t i = 0; i < f.size(); ++i) { o.off[i] = (uint32_t)at; std::memcpy(o.blob.data() + at, f[i].data(), f[i].size()); at += f[i].size(); }
+            o.off[f.size()] = (uint32_t)at;
+        };
+        const Dictionary& d = *dict_;
+        flatten(d.system.features, flat_[VBT_LEX_SYSTEM]);
+        if (d.has_user) flatten(d.user.features, flat_[VBT_LEX_USER]); else flat_[VBT_LEX_USER].off.assign(1, 0);
+        flatten(d.unk_features, flat_[VBT_LEX_UNKNOWN]);
+    });
+    return flat_;
+}
+
+const DevFeatures& Tokenizer::feature_table() const {
+    const FlatFeatures* flat = flat_features();
+    std::call_once(feat_once_, [&] {  // (a throw leaves the flag unset: the next caller tries again)
+        uint64_t bytes = 0, entries = 1;  // + the closing entry: index base + 1 of an EMPTY last lexicon is inside the array
+        for (int l = 0; l < 3; ++l) { bytes += flat[l].blob.size(); entries += flat[l].off.size(); }
+        if (bytes >= 0xFFFFFFFFull || entries >= 0xFFFFFFFFull) throw Error(VBT_ERR_UNSUPPORTED, "MeCab output on the device: more than 4 GiB of feature strings");
+        std::vector<uint32_t> off;
+        off.reserve(entries);
+        DevFeatures f{};
+        uint32_t at = 0;
+        for (int l = 0; l < 3; ++l) {
+            f.base[l] = (uint32_t)off.size();
+            f.words[l] = (uint32_t)flat[l].off.size() - 1u;
+            for (uint32_t o : flat[l].off) off.push_back(at + o);
+            at += (uint32_t)flat[l].blob.size();
+        }
+        off.push_back(at);
+        const size_t blob_alloc = ((size_t)bytes + 8 + 3) & ~(size_t)3;  // the zero slack behind the last feature
+        HIP_CHECK(hipSetDevice(device_));
+        void *d_blob = nullptr, *d_off = nullptr;
+        try {
+            HIP_CHECK(hipMalloc(&d_blob, blob_alloc));
+            HIP_CHECK(hipMalloc(&d_off, off.size() * 4));
+            HIP_CHECK(hipMemset(d_blob, 0, blob_alloc));
+            size_t pos = 0;
+            for (int l = 0; l < 3; ++l) {
+                if (!flat[l].blob.empty()) HIP_CHECK(hipMemcpy(static_cast<char*>(d_blob) + pos, flat[l].blob.data(), flat[l].blob.size(), hipMemcpyHostToDevice));
+                pos += flat[l].blob.size();
+            }
+            HIP_CHECK(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+            HIP_CHECK(hipDeviceSynchronize());  // (the fill and the copies have landed before a kernel of any stream reads the table)
+        } catch (...) {
+            if (d_blob) (void)hipFree(d_blob);
+            if (d_off) (void)hipFree(d_off);
+            throw;
+        }
+        f.blob = static_cast<const uint8_t*>(d_blob);
+        f.off = static_cast<const uint32_t*>(d_off);
+        feat_allocs_[0] = d_blob; feat_allocs_[1] = d_off;
+        feat_ = f;
+    });
+    return feat_;
 }
 
 double Tokenizer::candidates_per_byte() const {
@@ -436,6 +501,7 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
     last_n = n;
     last_stream = stream_;
     has_run = true;
+    mecab_ran = mecab;
     HIP_CHECK(hipMemsetAsync(d_ctrl, 0, (kCtrlWords + (size_t)kBlockCtrlWords) * 4, stream));  // ctrl + cctrl
     if (packed_slot && n > packed_max_s) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch has more sentences than the packed output slot holds");
     if (n == 0) {
@@ -444,6 +510,12 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
             BatchArgs a{};
             a.ctrl = d_ctrl;
             kern::wakati_lines(stream, a, 0, d_line_len, d_wakati_tiles, d_line_off, d_wakati, wakati_cap, false);
+            HIP_CHECK(hipGetLastError());
+        }
+        if (mecab) {
+            BatchArgs a{};
+            a.ctrl = d_ctrl;
+            kern::mecab_lines(stream, a, tok.feature_table(), 0, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, false);
             HIP_CHECK(hipGetLastError());
         }
         return;
@@ -658,8 +730,10 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
         // unless the batch is huge or the caller packs later and wants the grand total first)
         const bool scan_kernel = defer_pack || n_tiles > 2048 || env_u32("VBT_PACK_SCAN", 0);
         // (wakati mode: the lines are rendered from the staging regions; the records are packed only for a caller who wants both)
-        const bool records = !wakati || wakati_keep;
+        // (MeCab mode likewise; one text mode at a time)
+        const bool records = mecab ? mecab_keep : !wakati || wakati_keep;
         if (wakati) kern::wakati_lines(stream, a, n_tiles, d_line_len, d_wakati_tiles, d_line_off, d_wakati, wakati_cap, !records);
+        if (mecab) kern::mecab_lines(stream, a, tok.feature_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, !records);
         if (records && scan_kernel) kern::tok_tile_scan(stream, a, d_tile_sums, n_tiles);
         if (records && !defer_pack) kern::compact_tokens(stream, a, d_tile_sums, n_tiles, scan_kernel ? 1u : 0u);
         last_args = a;
@@ -701,7 +775,23 @@ void Workspace::set_packed_output(void* slot, uint64_t slot_bytes, uint64_t max_
     packed_slot = slot; packed_bytes = slot ? slot_bytes : 0; packed_max_s = slot ? max_s : 0;
 }
 
+// bytes per tile and the line offsets: the same for both text modes (nothing to clear: every word the caller may read is written by
+// the kernels of the batch)
+void Workspace::text_mode_buffers() {
+    HIP_CHECK(hipSetDevice(tok.device()));
+    const uint64_t ns = std::max<uint64_t>(max_sentences, 1);
+    auto alloc = [&](size_t bytes) {
+        void* p = nullptr;
+        HIP_CHECK(hipMalloc(&p, bytes));
+        pipe_allocs.push_back(p);
+        return p;
+    };
+    if (!d_wakati_tiles) d_wakati_tiles = static_cast<uint64_t*>(alloc(((ns + kScanTile - 1) / kScanTile + 1) * 8));
+    if (!d_line_off) d_line_off = static_cast<uint64_t*>(alloc((ns + 1) * 8));
+}
+
 void Workspace::set_wakati(bool on, bool keep_records, uint64_t cap_limit) {
+    if (on && mecab) throw Error(VBT_ERR_INVALID_ARGUMENT, "wakati mode: the workspace is in MeCab mode (one text mode at a time)");
     if (on && !d_wakati) {
         HIP_CHECK(hipSetDevice(tok.device()));
         const uint64_t ns = std::max<uint64_t>(max_sentences, 1), cap = 2 * max_bytes + ns;  // bytes + tokens (<= bytes) + a byte per sentence
@@ -711,10 +801,8 @@ void Workspace::set_wakati(bool on, bool keep_records, uint64_t cap_limit) {
             pipe_allocs.push_back(p);
             return p;
         };
-        // (nothing to clear: every word the caller may read is written by the kernels of the batch)
-        d_line_len = static_cast<uint32_t*>(alloc(ns * 4));
-        d_wakati_tiles = static_cast<uint64_t*>(alloc(((ns + kScanTile - 1) / kScanTile + 1) * 8));
-        d_line_off = static_cast<uint64_t*>(alloc((ns + 1) * 8));
+        text_mode_buffers();
+        if (!d_line_len) d_line_len = static_cast<uint32_t*>(alloc(ns * 4));
         d_wakati = static_cast<uint8_t*>(alloc(((cap + 3) & ~3ull) + kWakatiPad));
     }
     wakati = on;
@@ -723,6 +811,48 @@ void Workspace::set_wakati(bool on, bool keep_records, uint64_t cap_limit) {
         const uint64_t cap = 2 * max_bytes + std::max<uint64_t>(max_sentences, 1);
         wakati_cap = cap_limit ? std::min(cap, cap_limit) : cap;
     }
+}
+
+void Workspace::set_mecab(bool on, bool keep_records, uint64_t cap_bytes) {
+    if (on && wakati) throw Error(VBT_ERR_INVALID_ARGUMENT, "MeCab mode: the workspace is in wakati mode (one text mode at a time)");
+    if (on && cap_bytes == 0) throw Error(VBT_ERR_INVALID_ARGUMENT, "MeCab mode: cap_bytes must be > 0 (the input does not bound this output: the caller names the capacity)");
+    if (on) {
+        (void)tok.feature_table();  // uploaded by the first workspace that asks
+        HIP_CHECK(hipSetDevice(tok.device()));
+        text_mode_buffers();
+        if (!d_mecab_len) {
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, std::max<uint64_t>(max_sentences, 1) * 8));
+            pipe_allocs.push_back(p);
+            d_mecab_len = static_cast<uint64_t*>(p);
+        }
+        if (cap_bytes > mecab_alloc) {  // a larger buffer: the new one first (a failure leaves the old one in place), then the old one goes
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, ((cap_bytes + 3) & ~3ull) + kWakatiPad));
+            if (d_mecab) {
+                if (has_run) HIP_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(last_stream)));  // (a render may still be writing it)
+                pipe_allocs.erase(std::find(pipe_allocs.begin(), pipe_allocs.end(), static_cast<void*>(d_mecab)));
+                (void)hipFree(d_mecab);
+            }
+            pipe_allocs.push_back(p);
+            d_mecab = static_cast<uint8_t*>(p);
+            mecab_alloc = cap_bytes;
+        }
+        mecab_cap = cap_bytes;
+    }
+    mecab = on;
+    mecab_keep = on && keep_records;
+}
+
+void Workspace::render_text_again(void* stream_) {
+    if (!mecab || !mecab_ran) throw Error(VBT_ERR_INVALID_STATE, "render_text_again: the last run() of this workspace was not in MeCab mode");
+    HIP_CHECK(hipSetDevice(tok.device()));
+    last_stream = stream_;
+    BatchArgs a = last_args;
+    if (last_n == 0) { a = BatchArgs{}; a.ctrl = d_ctrl; }
+    kern::mecab_render_again(reinterpret_cast<hipStream_t>(stream_), a, tok.feature_table(), (uint32_t)((last_n + kScanTile - 1) / kScanTile), d_mecab_len,
+                             d_wakati_tiles, d_line_off, d_mecab, mecab_cap);
+    HIP_CHECK(hipGetLastError());
 }
 
 void Workspace::pack_to(vbt_token_rec* out_tokens, uint32_t* out_off, uint32_t* out_cnt, void* stream_) {

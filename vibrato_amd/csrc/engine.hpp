@@ -120,8 +120,24 @@ constexpr int kProfSlots = 256;  // the counters are spread over this many copie
 constexpr int kProfWords = 12;   // kProfPhases cycle totals, sentences, lattice steps, lattice passes, candidates
 constexpr int kProfPhases = 8;  // decode, count, fill, end lists, pre-pass, gather, recurrence, emit
 // kErrOffsets / kErrUtf8 are set by validate_batch; the batch is then skipped (no kernel touches the per-sentence regions)
-// kErrWakatiCap: a line of the wakati output would have ended beyond the output buffer (wakati_render; the line is not written)
+// kErrWakatiCap: the "text output capacity" flag of BOTH text modes: a line of the wakati output (wakati_render) or of the MeCab-format
+// output (mecab_render; also a line of 4 GiB and more) would have ended beyond the output buffer; the line is not written
 enum DevError { kErrTokCap = 1, kErrScratch = 2, kErrTooLong = 4, kErrOffsets = 8, kErrUtf8 = 16, kErrWakatiCap = 32, kErrFatal = kErrOffsets | kErrUtf8 };
+
+// The feature strings of the three lexicons (system, user, unknown) flat on the host: one blob per lexicon + a u32 offset per word id
+// and a terminator.  What vbt_batch_format reads, and what the device table below is built from.
+struct FlatFeatures { std::vector<uint32_t> off; std::vector<char> blob; };
+
+// The same on the device, for mecab.hip: ONE blob -- the three lexicons' feature bytes back to back + at least 8 zero bytes, so that
+// an aligned dword load around any feature's last byte stays inside the allocation -- and ONE offset array: the three off[] arrays,
+// each with its terminator, rebased into the blob (+ one closing entry).  Feature of word_idx = lex << 30 | id:
+// blob[off[base[lex] + id] .. off[base[lex] + id + 1]); words[lex] = ids of the lexicon (the kernels clamp to it).  Indexed by
+// word_idx, which the renumbering of the connection ids does not touch: one table serves every DevImage.
+struct DevFeatures {
+    const uint8_t* blob;
+    const uint32_t* off;
+    uint32_t base[3], words[3];
+};
 
 // What a kernel launch reads of the dictionary.  The connection ids inside it -- the rows and columns of the matrix, the id pairs of
 // the entry arrays -- are DEVICE ids: image 0 numbers them as the dictionary does; the image a tokenizer builds from the usage
@@ -178,6 +194,12 @@ class Tokenizer {
     // Workspace::run picks the sweep's tier set by it: dense lattices want 10 KiB segments, everything else 8 KiB ones and a fifth wave.
     double candidates_per_byte() const;
     unsigned long long* density_slot_dev() const { return density_dev_; }
+    // flat[VBT_LEX_SYSTEM .. VBT_LEX_UNKNOWN], built at the first call (a lexicon of 4 GiB of features and more: VBT_ERR_UNSUPPORTED)
+    const FlatFeatures* flat_features() const;
+    // The device table, uploaded at the first call -- by the first workspace of this tokenizer that enables MeCab mode, so a tokenizer
+    // that never renders MeCab text pays no HBM -- and freed with the tokenizer.  4 GiB of feature strings and more in all:
+    // VBT_ERR_UNSUPPORTED.  A failed upload leaves nothing allocated and is tried again by the next call.
+    const DevFeatures& feature_table() const;
 
   private:
     void upload_lexicon(const Lexicon& lx, DevLexicon& out);
@@ -208,6 +230,10 @@ class Tokenizer {
     mutable int calib_attempts_ = 0;
     unsigned long long* density_host_ = nullptr;  // {candidates, bytes}, pinned
     unsigned long long* density_dev_ = nullptr;   // the same, as the device sees it
+    mutable FlatFeatures flat_[3];
+    mutable std::once_flag flat_once_, feat_once_;
+    mutable DevFeatures feat_{};
+    mutable void* feat_allocs_[2] = {nullptr, nullptr};
 };
 
 class Workspace {
@@ -235,6 +261,22 @@ class Workspace {
     uint64_t* d_line_off = nullptr;
     uint64_t wakati_cap = 0;
     static constexpr uint64_t kWakatiPad = 64;  // bytes behind the capacity that are allocated and never written
+    // MeCab output mode (mecab.hip): every later run() also leaves the MeCab-format text of the batch -- per token "surface \t
+    // feature \n", per sentence "EOS\n", lines back to back -- in d_mecab and the lines' byte offsets in d_line_off[n + 1], rendered
+    // from the staging regions behind the sweeps; the token records are packed only when keep_records is set.  One text mode at a
+    // time: enabling this one while wakati mode is on, or the reverse, is VBT_ERR_INVALID_ARGUMENT.
+    // The input does not bound this output, so the CALLER names the capacity: cap_bytes (> 0 when enabling) is what the kernels may
+    // use; the buffer is allocated, or replaced by a larger one, when more is asked for than it holds (+ kWakatiPad bytes behind it
+    // that are never written).  A line that would end beyond the capacity sets kErrWakatiCap and is not written, the lines in front
+    // of it are; d_line_off[n] is the exact need either way.
+    void set_mecab(bool on, bool keep_records, uint64_t cap_bytes);
+    // Valid after a run() in MeCab mode until the next run(), with the batch's text and offsets still in place: takes the capacity
+    // flag back on `stream` and renders the lines once more (mecab_render alone: the staging regions, the line lengths and the tile
+    // prefix of the run still hold) -- after set_mecab with a larger capacity, growing costs one render, not a second tokenisation.
+    void render_text_again(void* stream);
+    bool mecab = false, mecab_keep = false;
+    uint8_t* d_mecab = nullptr;
+    uint64_t mecab_cap = 0, mecab_alloc = 0;  // bytes the kernels may use / bytes the buffer holds in front of its pad
     void* packed_slot = nullptr;
     uint64_t packed_bytes = 0, packed_max_s = 0;
     void stats(vbt_call_stats* out);  // synchronizes the last stream used
@@ -286,8 +328,11 @@ class Workspace {
     void* ev[4] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t* d_line_len = nullptr;      // wakati mode: bytes per line, bytes per tile of kScanTile lines
     uint64_t* d_wakati_tiles = nullptr;
+    uint64_t* d_mecab_len = nullptr;     // MeCab mode: bytes per line (d_wakati_tiles and d_line_off serve both text modes)
+    bool mecab_ran = false;              // the last run() rendered MeCab text: render_text_again may follow
 
   private:
+    void text_mode_buffers();  // d_wakati_tiles, d_line_off: allocated by the text mode that is enabled first
     void release();  // frees every device allocation, stream and event (also on a constructor failure)
 };
 

@@ -1,4 +1,4 @@
-// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip, wakati.hip), as plain
+// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip, wakati.hip, mecab.hip), as plain
 // functions the host side (engine.hip: Tokenizer, Workspace) calls.  Every launcher enqueues on `stream` and returns.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -61,6 +61,19 @@ void permute_matrix(hipStream_t stream, const void* src, void* dst, bool wide, c
 uint32_t wakati_round();  // tokens per LDS round of wakati_render
 void wakati_lines(hipStream_t stream, const BatchArgs& a, uint32_t n_tiles, uint32_t* line_len, uint64_t* tile_bytes, uint64_t* line_off, uint8_t* out,
                   uint64_t out_cap, bool count_tokens);
+// wakati_scan alone: the prefix both text modes take over their tiles' bytes
+void text_tile_scan(hipStream_t stream, const BatchArgs& a, uint64_t* tile_bytes, uint32_t n_tiles, uint64_t* line_off, bool count_tokens);
+
+// ---- mecab.hip: the MeCab-format text of a batch ("surface \t feature \n" per token, "EOS\n" per sentence) from the staging regions
+// and the feature table `f`.  mecab_plan (line_len[n] u64, bytes per tile) -> text_tile_scan -> mecab_render (line_off[0 .. n), the
+// lines into out; a line that would end beyond out_cap, or of 4 GiB and more, sets kErrWakatiCap and is not written; line_off[n] is
+// the exact total either way).  mecab_render_again: takes that flag back and renders once more, into another buffer or capacity;
+// line_len / tile_bytes / the staging regions of the batch must be what mecab_lines left.
+uint32_t mecab_round();  // tokens per LDS round of mecab_render
+void mecab_lines(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, uint32_t n_tiles, uint64_t* line_len, uint64_t* tile_bytes, uint64_t* line_off,
+                 uint8_t* out, uint64_t out_cap, bool count_tokens);
+void mecab_render_again(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, uint32_t n_tiles, const uint64_t* line_len, const uint64_t* tile_bytes,
+                        uint64_t* line_off, uint8_t* out, uint64_t out_cap);
 
 // the calibration sample (Tokenizer::maybe_calibrate): up to `want` sentences spread evenly over the batch, copied into s_text / s_offs
 // (s_offs[0 .. k], k = info[0] = the sentences whose text fits cap_bytes; s_src: want words of scratch), on `stream`

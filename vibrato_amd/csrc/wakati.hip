@@ -54,6 +54,7 @@ __global__ void __launch_bounds__(kWakatiBlock) wakati_plan(BatchArgs A, uint32_
 // adds up a run of tiles, the runs' prefix is taken out of LDS.  (One path for every batch size: a launch of its own costs the
 // call ~3 us, adding the tiles up inside wakati_render would need this kernel anyway beyond a few thousand tiles.)
 // count_tokens: the records are not packed for this batch, so the grand total of tile_sums[] is left in ctrl[kTotal] here.
+// (Shared with the MeCab-format renderer, mecab.hip, through kern::text_tile_scan: the same prefix over its tiles' bytes.)
 __global__ void __launch_bounds__(1024) wakati_scan(BatchArgs A, uint64_t* __restrict__ tile_bytes, uint32_t n_tiles, uint64_t* __restrict__ line_off,
                                                     uint32_t count_tokens) {
     __shared__ uint64_t part[1024];
@@ -175,10 +176,13 @@ __global__ void __launch_bounds__(kWakatiBlock) wakati_render(BatchArgs A, const
 namespace kern {
 
 uint32_t wakati_round() { return kWakatiRound; }
+void text_tile_scan(hipStream_t stream, const BatchArgs& a, uint64_t* tile_bytes, uint32_t n_tiles, uint64_t* line_off, bool count_tokens) {
+    hipLaunchKernelGGL(vbt::wakati_scan, dim3(1), dim3(1024), 0, stream, a, tile_bytes, n_tiles, line_off, count_tokens ? 1u : 0u);
+}
 void wakati_lines(hipStream_t stream, const BatchArgs& a, uint32_t n_tiles, uint32_t* line_len, uint64_t* tile_bytes, uint64_t* line_off, uint8_t* out,
                   uint64_t out_cap, bool count_tokens) {
     if (n_tiles) hipLaunchKernelGGL(vbt::wakati_plan, dim3(n_tiles), dim3(kWakatiBlock), 0, stream, a, line_len, tile_bytes);
-    hipLaunchKernelGGL(vbt::wakati_scan, dim3(1), dim3(1024), 0, stream, a, tile_bytes, n_tiles, line_off, count_tokens ? 1u : 0u);
+    text_tile_scan(stream, a, tile_bytes, n_tiles, line_off, count_tokens);
     if (n_tiles) hipLaunchKernelGGL(vbt::wakati_render, dim3(n_tiles), dim3(kWakatiBlock), 0, stream, a, line_len, tile_bytes, line_off, out, out_cap);
 }
 
