@@ -285,6 +285,15 @@ VBT_API int vbt_tokenize_wakati(const vbt_tokenizer* tok, const uint8_t* text, c
  * with VBT_ERR_UNSUPPORTED: sharded rendering is not implemented. */
 VBT_API int vbt_tokenize_mecab(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
                                char** out, size_t* len, uint64_t* line_off);
+/* Host text in -> detail text out (tokenize/src/main.rs:108-123: per token "surface \t feature \tlex_type=System|User|Unknown
+ * \tleft_id=N \tright_id=N \tword_cost=N \ttotal_cost=N \n", then "EOS\n"), rendered ON THE DEVICE: the same bytes as
+ * vbt_tokenize_batch + vbt_batch_format(VBT_FORMAT_DETAIL), with the contract of vbt_tokenize_mecab in everything -- one unpipelined
+ * call on a pooled workspace, the first capacity from the largest output-per-input ratio seen FOR THIS MODE (+ 1/8 + 4 n; 16 x bytes
+ * + 4 n before any batch; VBT_DETAIL_FIRST_CAP = bytes in the environment, read per call, overrides it -- VBT_MECAB_FIRST_CAP does
+ * not apply here), at most one re-render, *out released ONLY with vbt_free, VBT_ERR_UNSUPPORTED for a multi-device tokenizer.  The
+ * ids printed are the dictionary's, from a word-parameter table of the device image uploaded at the first call. */
+VBT_API int vbt_tokenize_detail(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
+                                char** out, size_t* len, uint64_t* line_off);
 
 /* ---- Device-resident API (zero-copy; what bench.py times) ------------------------ */
 
@@ -357,15 +366,26 @@ VBT_API int vbt_workspace_wakati(const vbt_workspace* ws, const uint8_t** d_out,
 VBT_API int vbt_workspace_set_mecab(vbt_workspace* ws, int enabled, int keep_records, uint64_t cap_bytes);
 VBT_API int vbt_workspace_mecab(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off /* n + 1 */);
 VBT_API int vbt_workspace_render_again(vbt_workspace* ws, void* hip_stream);
+/* Detail output on the device (tokenize/src/main.rs:108-123).  As MeCab mode, with every token's line extended by "\tlex_type=..
+ * \tleft_id=.. \tright_id=.. \tword_cost=.. \ttotal_cost=.." in front of its newline: the ids and the word cost are the
+ * dictionary's (a word-parameter table of the device image, uploaded when the first workspace of a tokenizer enables the mode),
+ * the decimal fields are converted on the device.  cap_bytes, flag 32, d_line_off[n], the 64-byte pad and vbt_workspace_render_again
+ * (tokenize/src/main.rs:108-123: it serves whichever of the two modes the last call used) are MeCab mode's; the two modes share one
+ * output buffer.  One text mode at a time among the three: enabling one while another is on is VBT_ERR_INVALID_ARGUMENT.  A wave
+ * renders a sentence VBT_DETAIL_ROUND tokens at a time.
+ * vbt_workspace_detail (tokenize/src/main.rs:108-123): as vbt_workspace_mecab. */
+#define VBT_DETAIL_ROUND 64
+VBT_API int vbt_workspace_set_detail(vbt_workspace* ws, int enabled, int keep_records, uint64_t cap_bytes);
+VBT_API int vbt_workspace_detail(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off /* n + 1 */);
 /* Per-call statistics (synchronizes the stream of the last call): how many sentences were filed
  * in the LDS tiers sentences are routed to up front -- the lean tier and the segment tier (n_tier0) --, in the escape tiers behind
  * them (n_tier1: what a sweep passed on) and in the list of the global-memory fallback kernel (n_tier2; a re-routed sentence is
  * counted in every list it was filed in), tokens
  * written, device error flags (1 = token buffer full, 2 = scratch exhausted, 4 = sentence too
- * long, 8 = bad offsets, 16 = invalid UTF-8, 32 = a line of the text output -- wakati or MeCab mode -- did not fit the output buffer) and, with timing enabled, the hipEvent-measured durations (ms, on the launch stream) of the
+ * long, 8 = bad offsets, 16 = invalid UTF-8, 32 = a line of the text output -- wakati, MeCab or detail mode -- did not fit the output buffer) and, with timing enabled, the hipEvent-measured durations (ms, on the launch stream) of the
  * input check and the candidate generators (ms_tier0: validate_batch, gen_candidates, build_lists, the gen_long levels), of the
  * lattice sweeps from their fork to their join (ms_tier12) and of what follows -- the global-memory fallback launch and the packing
- * of the token records and, in wakati or MeCab mode, the three kernels that render the lines (ms_pack). */
+ * of the token records and, in wakati, MeCab or detail mode, the three kernels that render the lines (ms_pack). */
 typedef struct vbt_call_stats {
     uint64_t n_sentences, n_tier0, n_tier1, n_tier2, n_tokens;
     uint32_t error_flags;

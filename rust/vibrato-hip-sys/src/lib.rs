@@ -150,6 +150,8 @@ extern "C" {
                                line_off: *mut u64) -> c_int;
     pub fn vbt_tokenize_mecab(tok: *const vbt_tokenizer, text: *const u8, offsets: *const u64, n: u64, out: *mut *mut c_char, len: *mut usize,
                               line_off: *mut u64) -> c_int;
+    pub fn vbt_tokenize_detail(tok: *const vbt_tokenizer, text: *const u8, offsets: *const u64, n: u64, out: *mut *mut c_char, len: *mut usize,
+                               line_off: *mut u64) -> c_int;
 
     // ---- Device-resident API
     pub fn vbt_workspace_new(tok: *const vbt_tokenizer, max_sentences: u64, max_bytes: u64, out: *mut *mut vbt_workspace) -> c_int;
@@ -163,6 +165,8 @@ extern "C" {
     pub fn vbt_workspace_wakati(ws: *const vbt_workspace, d_out: *mut *const u8, d_line_off: *mut *const u64) -> c_int;
     pub fn vbt_workspace_set_mecab(ws: *mut vbt_workspace, enabled: c_int, keep_records: c_int, cap_bytes: u64) -> c_int;
     pub fn vbt_workspace_mecab(ws: *const vbt_workspace, d_out: *mut *const u8, d_line_off: *mut *const u64) -> c_int;
+    pub fn vbt_workspace_set_detail(ws: *mut vbt_workspace, enabled: c_int, keep_records: c_int, cap_bytes: u64) -> c_int;
+    pub fn vbt_workspace_detail(ws: *const vbt_workspace, d_out: *mut *const u8, d_line_off: *mut *const u64) -> c_int;
     pub fn vbt_workspace_render_again(ws: *mut vbt_workspace, hip_stream: *mut c_void) -> c_int;
     pub fn vbt_workspace_set_timing(ws: *mut vbt_workspace, enabled: c_int) -> c_int;
     pub fn vbt_workspace_count_connids(ws: *mut vbt_workspace, enabled: c_int) -> c_int;

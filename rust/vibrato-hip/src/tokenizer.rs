@@ -159,6 +159,13 @@ impl Tokenizer {
         self.tokenize_text_raw(sys::vbt_tokenize_mecab, text, offsets)
     }
 
+    /// Detail output of many sentences (`tokenize/src/main.rs:108-123`: every token's line extended by its lexicon, connection
+    /// ids and costs), rendered on the device (new): the bytes of `tokenize_batch(..)?.format(OutputMode::Detail)`. Returns as
+    /// `tokenize_wakati_raw` does. Single-device tokenizers only.
+    pub fn tokenize_detail_raw(&self, text: &[u8], offsets: &[u64]) -> Result<(String, Vec<u64>)> {
+        self.tokenize_text_raw(sys::vbt_tokenize_detail, text, offsets)
+    }
+
     fn tokenize_text_raw(
         &self,
         call: unsafe extern "C" fn(*const sys::vbt_tokenizer, *const u8, *const u64, u64, *mut *mut std::os::raw::c_char, *mut usize, *mut u64) -> std::os::raw::c_int,

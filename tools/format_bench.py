@@ -2,7 +2,8 @@
 """Developer aid: vbt_batch_format call by call on one headline-sized batch (cold / warm buffer, thread counts).
 usage (GPU box): python tools/format_bench.py [threads ...]
                  python tools/format_bench.py --wakati    (wakati text: host formatter route against the device route)
-                 python tools/format_bench.py --mecab     (MeCab-format text: the same two routes)"""
+                 python tools/format_bench.py --mecab     (MeCab-format text: the same two routes)
+                 python tools/format_bench.py --detail    (detail text: the same two routes)"""
 import ctypes as C
 import os
 import subprocess
@@ -35,8 +36,8 @@ def one():
 
 
 def routes(mode, rounds=12, calls=8):
-    """Text in -> wakati / MeCab-format text out on one headline-sized batch, one caller thread, one process: the host route
-    (vbt_tokenize_batch + vbt_batch_format + the frees) against the device route (vbt_tokenize_wakati / vbt_tokenize_mecab + vbt_free),
+    """Text in -> wakati / MeCab-format / detail text out on one headline-sized batch, one caller thread, one process: the host route
+    (vbt_tokenize_batch + vbt_batch_format + the frees) against the device route (vbt_tokenize_wakati / vbt_tokenize_mecab / vbt_tokenize_detail + vbt_free),
     alternating, `calls` calls per timed window; medians, the run-to-run spread of either route, the bytes that leave the device per
     batch, and ms_pack of the device-resident call (the fallback launch + the record packing, or + the three kernels of the text
     mode) with and without the text mode."""
@@ -55,7 +56,7 @@ def routes(mode, rounds=12, calls=8):
     def host():
         b, p, ln = C.c_void_p(), C.c_void_p(), C.c_size_t()
         N.check(L.vbt_tokenize_batch(h, text.ctypes.data, offs.ctypes.data, n, C.byref(b)))
-        N.check(L.vbt_batch_format(b, 1 if mode == "wakati" else 0, C.byref(p), C.byref(ln)))
+        N.check(L.vbt_batch_format(b, {"mecab": 0, "wakati": 1, "detail": 2}[mode], C.byref(p), C.byref(ln)))
         nt = L.vbt_batch_total_tokens(b)
         L.vbt_free(p)
         L.vbt_batch_free(b)
@@ -91,8 +92,10 @@ def routes(mode, rounds=12, calls=8):
     for on in (False, True):
         if mode == "wakati":
             ws.set_wakati(on)
-        else:
+        elif mode == "mecab":
             ws.set_mecab(on, cap_bytes=len(ref))
+        else:
+            ws.set_detail(on, cap_bytes=len(ref))
         v = []
         for _ in range(10):
             ws.run(d_text.data_ptr(), d_offs.data_ptr(), n, len(text), torch.cuda.current_stream().cuda_stream)
@@ -101,7 +104,7 @@ def routes(mode, rounds=12, calls=8):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("--wakati", "--mecab"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("--wakati", "--mecab", "--detail"):
         routes(sys.argv[1][2:])
     elif len(sys.argv) > 1 and sys.argv[1] == "--one":
         one()

@@ -42,6 +42,7 @@ class CallStats(C.Structure):
 
 WAKATI_ROUND = 256  # VBT_WAKATI_ROUND of include/vibrato_hip.h: tokens per LDS round of the wakati render kernel
 MECAB_ROUND = 128   # VBT_MECAB_ROUND: the same of the MeCab-format render kernel
+DETAIL_ROUND = 64   # VBT_DETAIL_ROUND: the same of the detail render kernel
 
 # name -> (restype, argtypes); also the list of symbols include/vibrato_hip.h declares.
 _vp, _cp, _sz, _u32, _u64, _int = C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
@@ -103,6 +104,7 @@ SIGNATURES = {
     "vbt_free": (None, [_vp]),
     "vbt_tokenize_wakati": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
     "vbt_tokenize_mecab": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
+    "vbt_tokenize_detail": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
     "vbt_workspace_new": (_int, [_vp, _u64, _u64, _PP]),
     "vbt_workspace_free": (None, [_vp]),
     "vbt_tokenize_batch_device": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
@@ -112,6 +114,8 @@ SIGNATURES = {
     "vbt_workspace_wakati": (_int, [_vp, _PP, _PP]),
     "vbt_workspace_set_mecab": (_int, [_vp, _int, _int, _u64]),
     "vbt_workspace_mecab": (_int, [_vp, _PP, _PP]),
+    "vbt_workspace_set_detail": (_int, [_vp, _int, _int, _u64]),
+    "vbt_workspace_detail": (_int, [_vp, _PP, _PP]),
     "vbt_workspace_render_again": (_int, [_vp, _vp]),
     "vbt_workspace_set_timing": (_int, [_vp, _int]),
     "vbt_workspace_count_connids": (_int, [_vp, _int]),

@@ -342,6 +342,13 @@ class Tokenizer:
         host formatter threads.  Returns as tokenize_wakati does.  Single-device tokenizers only."""
         return self._tokenize_text(N.lib().vbt_tokenize_mecab, sentences, text, offsets, with_offsets)
 
+    def tokenize_detail(self, sentences=None, text=None, offsets=None, with_offsets=False):
+        """Host text in -> detail text out (tokenize/src/main.rs:108-123: per token "surface\\tfeature\\tlex_type=..\\tleft_id=..
+        \\tright_id=..\\tword_cost=..\\ttotal_cost=..\\n", "EOS\\n" per sentence), rendered on the device (vbt_tokenize_detail): the
+        bytes of tokenize_batch(...).format("detail") without token records or host formatter threads.  Returns as tokenize_wakati
+        does.  Single-device tokenizers only."""
+        return self._tokenize_text(N.lib().vbt_tokenize_detail, sentences, text, offsets, with_offsets)
+
     def _tokenize_text(self, call, sentences, text, offsets, with_offsets):
         if sentences is not None:
             enc = [_b(s) for s in sentences]
@@ -724,7 +731,7 @@ class Workspace:
         """Every later run() also renders the batch's MeCab-format text on the device (mecab_ptrs); the token records are packed
         only with keep_records.  cap_bytes (> 0 when enabling): the capacity of the output buffer, which the input does not bound;
         a line that would end beyond it sets error flag 32 and is not written, line_off[n] is the exact need either way.  Not
-        while wakati mode is on."""
+        while wakati or detail mode is on."""
         N.check(N.lib().vbt_workspace_set_mecab(self._h, int(bool(on)), int(keep_records), int(cap_bytes)))
 
     def mecab_ptrs(self):
@@ -733,9 +740,20 @@ class Workspace:
         N.check(N.lib().vbt_workspace_mecab(self._h, C.byref(o), C.byref(lo)))
         return {"out": o.value, "line_off": lo.value}
 
+    def set_detail(self, on=True, keep_records=False, cap_bytes=0):
+        """Every later run() also renders the batch's detail text on the device (detail_ptrs), with set_mecab's arguments, capacity
+        rule and output buffer.  Not while wakati or MeCab mode is on."""
+        N.check(N.lib().vbt_workspace_set_detail(self._h, int(bool(on)), int(keep_records), int(cap_bytes)))
+
+    def detail_ptrs(self):
+        """As mecab_ptrs, of the last run() in detail mode."""
+        o, lo = C.c_void_p(), C.c_void_p()
+        N.check(N.lib().vbt_workspace_detail(self._h, C.byref(o), C.byref(lo)))
+        return {"out": o.value, "line_off": lo.value}
+
     def render_again(self, stream):
-        """After a run() in MeCab mode, before the next one: clears error flag 32 and renders the lines once more on `stream` --
-        with a larger set_mecab(cap_bytes=...) in between, growing the buffer costs one render, not a second tokenisation."""
+        """After a run() in MeCab or detail mode, before the next one: clears error flag 32 and renders the lines once more on `stream` --
+        with a larger set_mecab / set_detail(cap_bytes=...) in between, growing the buffer costs one render, not a second tokenisation."""
         N.check(N.lib().vbt_workspace_render_again(self._h, stream or None))
 
     def result_ptrs(self):

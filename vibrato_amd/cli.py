@@ -54,12 +54,12 @@ def main(argv=None, stdin=None, stdout=None):
     # Three stages, each on its own thread (the library calls release the GIL): this thread reads lines and cuts blocks, one thread
     # pushes block k + 1 through the GPU (vbt_tokenize_batch), one renders block k (vbt_batch_format) and writes it -- the formatter
     # of one block runs under the kernels and copies of the next.  Output order = input order (one block at a time per stage).
-    # (-O wakati and -O mecab: the block's text is rendered on the device -- Tokenizer.tokenize_wakati / tokenize_mecab -- and the
-    # output stage only writes it)
+    # (on a single-device tokenizer the block's text is rendered on the device in every output mode -- Tokenizer.tokenize_wakati /
+    # tokenize_mecab / tokenize_detail -- and the output stage only writes it; DESIGN.md 3.4a-c hold the measurements behind that)
     import queue
     import threading
-    text_on_device = args.output_mode in ("wakati", "mecab") and tok.num_devices() == 1
-    tokenize_text = tok.tokenize_wakati if args.output_mode == "wakati" else tok.tokenize_mecab
+    text_on_device = tok.num_devices() == 1
+    tokenize_text = {"wakati": tok.tokenize_wakati, "mecab": tok.tokenize_mecab, "detail": tok.tokenize_detail}[args.output_mode]
     blocks, batches = queue.Queue(maxsize=2), queue.Queue(maxsize=2)
     failure = []
 

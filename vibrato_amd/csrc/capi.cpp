@@ -234,6 +234,8 @@ struct vbt_tokenizer {
     std::atomic<uint32_t> tok_per_kib{0};
     // bytes of MeCab-format output per KiB of text, likewise: the first capacity of vbt_tokenize_mecab
     std::atomic<uint32_t> mecab_per_kib{0};
+    // ... and of detail output (its lines are longer: a ratio of its own): the first capacity of vbt_tokenize_detail
+    std::atomic<uint32_t> detail_per_kib{0};
     // vbt_tokenize_batch calls running right now, calls started so far, and the last call that saw another one in flight: only a
     // caller that has been alone for a while gets its batch pipelined in chunks (host threads that stream batches side by side
     // overlap each other's copies and kernels already; a chunked call in their midst is slower for everybody)
@@ -341,7 +343,7 @@ void check_device_errors(uint32_t flags) {
     if (flags & kErrTokCap) throw Error(VBT_ERR_INVALID_STATE, "device token buffer overflow");
     if (flags & kErrScratch) throw Error(VBT_ERR_UNSUPPORTED, "device scratch arena exhausted (raise VBT_SCRATCH_MB)");
     if (flags & kErrTooLong) throw Error(VBT_ERR_UNSUPPORTED, "sentence too long for the device image (>= 4 GiB or >= 2^32 lattice nodes)");
-    if (flags & kErrWakatiCap) throw Error(VBT_ERR_INVALID_STATE, "device text output buffer overflow (wakati or MeCab mode)");
+    if (flags & kErrWakatiCap) throw Error(VBT_ERR_INVALID_STATE, "device text output buffer overflow (wakati, MeCab or detail mode)");
 }
 
 // Token accessors (token.rs:21-92) from a raw record.
@@ -1498,14 +1500,20 @@ int vbt_tokenize_batch(const vbt_tokenizer* tok_, const uint8_t* text, const uin
 // MeCab format (mecab.hip) likewise, plus the capacity protocol: the input does not bound that output, so the call names a first
 // capacity -- from the largest output-per-input ratio the tokenizer has seen -- and a batch that does not fit (error flag 32 alone)
 // is rendered once more into a buffer of the exact size the device reported (Workspace::render_text_again), not tokenized again.
-static int tokenize_text_on_device(bool mecab, const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len,
+// Detail text (detail.hip; tokenize/src/main.rs:108-123) is MeCab format's protocol with a ratio and an environment override of its own.
+enum TextMode { kTextWakati, kTextMecab, kTextDetail };
+static int tokenize_text_on_device(TextMode mode, const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len,
                                    uint64_t* line_off) {
     return guarded([&] {
         vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
         if (!tok || !offsets || !out || !len || (!text && n && offsets[n] != offsets[0])) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
         if (tok->reps.size() > 1)
-            throw Error(VBT_ERR_UNSUPPORTED, mecab ? "vbt_tokenize_mecab: a multi-device tokenizer cannot render MeCab output (sharded rendering is not implemented)"
-                                                   : "vbt_tokenize_wakati: a multi-device tokenizer cannot render wakati output (sharded rendering is not implemented)");
+            throw Error(VBT_ERR_UNSUPPORTED, mode == kTextDetail  ? "vbt_tokenize_detail: a multi-device tokenizer cannot render detail output (sharded rendering is not implemented)"
+                                             : mode == kTextMecab ? "vbt_tokenize_mecab: a multi-device tokenizer cannot render MeCab output (sharded rendering is not implemented)"
+                                                                  : "vbt_tokenize_wakati: a multi-device tokenizer cannot render wakati output (sharded rendering is not implemented)");
+        const bool mecab = mode != kTextWakati;  // the capacity protocol: MeCab and detail mode
+        const bool detail = mode == kTextDetail;
+        std::atomic<uint32_t>& per_kib = detail ? tok->detail_per_kib : tok->mecab_per_kib;
         const uint64_t lo = offsets[0];
         for (uint64_t i = 1; i <= n; ++i)
             if (offsets[i] < offsets[i - 1]) throw Error(VBT_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
@@ -1532,6 +1540,7 @@ static int tokenize_text_on_device(bool mecab, const vbt_tokenizer* tok_, const 
                     (void)hipStreamSynchronize(p->stream);
                     p->ws->set_wakati(false, false);
                     p->ws->set_mecab(false, false, 0);
+                    p->ws->set_detail(false, false, 0);
                     pool_give(tok, rep, std::move(p));
                 }
                 host_give(tok, std::move(blk));
@@ -1555,10 +1564,11 @@ static int tokenize_text_on_device(bool mecab, const vbt_tokenizer* tok_, const 
         if (mecab) {
             // first capacity: the running maximum of output bytes per KiB of input + 1/8 + "EOS\n" per sentence; 8 x the input before
             // any batch has been seen; VBT_MECAB_FIRST_CAP (bytes, read per call: tests, A/B runs) overrides
-            const uint32_t r = tok->mecab_per_kib.load(std::memory_order_relaxed);
-            uint64_t cap = (r ? (bytes * r / 1024) * 9 / 8 : 8 * bytes) + 4 * n;
-            if (const char* e = std::getenv("VBT_MECAB_FIRST_CAP")) { const uint64_t v = std::strtoull(e, nullptr, 10); if (v) cap = v; }
-            p.ws->set_mecab(true, false, cap);
+            // (detail mode: 16 x, VBT_DETAIL_FIRST_CAP)
+            const uint32_t r = per_kib.load(std::memory_order_relaxed);
+            uint64_t cap = (r ? (bytes * r / 1024) * 9 / 8 : (detail ? 16 : 8) * bytes) + 4 * n;
+            if (const char* e = std::getenv(detail ? "VBT_DETAIL_FIRST_CAP" : "VBT_MECAB_FIRST_CAP")) { const uint64_t v = std::strtoull(e, nullptr, 10); if (v) cap = v; }
+            if (detail) p.ws->set_detail(true, false, cap); else p.ws->set_mecab(true, false, cap);
         } else {
             p.ws->set_wakati(true, false);
         }
@@ -1573,18 +1583,18 @@ static int tokenize_text_on_device(bool mecab, const vbt_tokenizer* tok_, const 
                 if (!valid_utf8(txt + offs[i], offs[i + 1] - offs[i])) throw Error(VBT_ERR_UTF8, "sentence " + std::to_string(i) + " is not valid UTF-8");
         }
         if (mecab && tail[1] == (uint32_t)kErrWakatiCap) {  // the capacity alone: the exact need is known now -- grow, render once more
-            p.ws->set_mecab(true, false, *total);
+            if (detail) p.ws->set_detail(true, false, *total); else p.ws->set_mecab(true, false, *total);
             p.ws->render_text_again(p.stream);
             HIPX(hipMemcpyAsync(tail, p.ws->d_ctrl, 8, hipMemcpyDeviceToHost, p.stream));
             HIPX(hipStreamSynchronize(p.stream));
-            if (tail[1] & kErrWakatiCap) throw Error(VBT_ERR_DEVICE, "vbt_tokenize_mecab: the text does not fit a buffer of the size the device asked for");
+            if (tail[1] & kErrWakatiCap) throw Error(VBT_ERR_DEVICE, "vbt_tokenize_mecab / vbt_tokenize_detail: the text does not fit a buffer of the size the device asked for");
         }
         check_device_errors(tail[1]);
         const size_t out_bytes = (size_t)*total;
         if (mecab && bytes) {  // bytes of output per KiB of text, rounded up: the largest seen
             const uint32_t r = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, ((uint64_t)out_bytes * 1024 + bytes - 1) / bytes + 1);
-            uint32_t cur = tok->mecab_per_kib.load(std::memory_order_relaxed);
-            while (r > cur && !tok->mecab_per_kib.compare_exchange_weak(cur, r, std::memory_order_relaxed)) {}
+            uint32_t cur = per_kib.load(std::memory_order_relaxed);
+            while (r > cur && !per_kib.compare_exchange_weak(cur, r, std::memory_order_relaxed)) {}
         }
         h.result = pin_out_alloc(out_bytes);
         const void* src[2] = {mecab ? p.ws->d_mecab : p.ws->d_wakati, p.ws->d_line_off};
@@ -1607,11 +1617,15 @@ static int tokenize_text_on_device(bool mecab, const vbt_tokenizer* tok_, const 
 }
 
 int vbt_tokenize_wakati(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len, uint64_t* line_off) {
-    return tokenize_text_on_device(false, tok, text, offsets, n, out, len, line_off);
+    return tokenize_text_on_device(kTextWakati, tok, text, offsets, n, out, len, line_off);
 }
 
 int vbt_tokenize_mecab(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len, uint64_t* line_off) {
-    return tokenize_text_on_device(true, tok, text, offsets, n, out, len, line_off);
+    return tokenize_text_on_device(kTextMecab, tok, text, offsets, n, out, len, line_off);
+}
+
+int vbt_tokenize_detail(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len, uint64_t* line_off) {
+    return tokenize_text_on_device(kTextDetail, tok, text, offsets, n, out, len, line_off);
 }
 
 // Releases every idle pooled workspace and pinned block now (they are re-created on demand).
@@ -1909,6 +1923,22 @@ int vbt_workspace_mecab(const vbt_workspace* ws, const uint8_t** d_out, const ui
         if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
         if (!ws->w->d_mecab) throw Error(VBT_ERR_INVALID_STATE, "MeCab output was never enabled on this workspace (vbt_workspace_set_mecab)");
         if (d_out) *d_out = ws->w->d_mecab;
+        if (d_line_off) *d_line_off = ws->w->d_line_off;
+    });
+}
+
+int vbt_workspace_set_detail(vbt_workspace* ws, int enabled, int keep_records, uint64_t cap_bytes) {
+    return guarded([&] {
+        if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null workspace");
+        ws->w->set_detail(enabled != 0, keep_records != 0, cap_bytes);
+    });
+}
+
+int vbt_workspace_detail(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off) {
+    return guarded([&] {
+        if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (!ws->w->d_mecab) throw Error(VBT_ERR_INVALID_STATE, "detail output was never enabled on this workspace (vbt_workspace_set_detail)");
+        if (d_out) *d_out = ws->w->d_mecab;  // (the buffer MeCab and detail mode share)
         if (d_line_off) *d_line_off = ws->w->d_line_off;
     });
 }

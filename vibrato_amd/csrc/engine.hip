@@ -241,6 +241,7 @@ Tokenizer::~Tokenizer() {
         for (void* p : im->allocs) (void)hipFree(p);
     for (void* p : allocs_) (void)hipFree(p);
     for (void* p : feat_allocs_) if (p) (void)hipFree(p);
+    if (wparam_alloc_) (void)hipFree(wparam_alloc_);
     if (density_host_) (void)hipHostFree(density_host_);
 }
 
@@ -306,6 +307,44 @@ const DevFeatures& Tokenizer::feature_table() const {
         feat_ = f;
     });
     return feat_;
+}
+
+const DevWordParams& Tokenizer::word_param_table() const {
+    std::call_once(wparam_once_, [&] {  // (a throw leaves the flag unset: the next caller tries again)
+        const Dictionary& d = *dict_;
+        const size_t n_user = d.has_user ? d.user.params.size() : 0;
+        const uint64_t entries = (uint64_t)d.system.params.size() + n_user + d.unk_entries.size() + 1;  // + the closing entry
+        if (entries >= 0xFFFFFFFFull) throw Error(VBT_ERR_UNSUPPORTED, "detail output on the device: more than 2^32 words");
+        std::vector<DevWordParam> e;
+        e.reserve(entries);
+        DevWordParams w{};
+        auto lexicon = [&](int l, const std::vector<WordParam>& ps) {
+            w.base[l] = (uint32_t)e.size();
+            w.words[l] = (uint32_t)ps.size();
+            for (const WordParam& p : ps) e.push_back(DevWordParam{p.left_id, p.right_id, p.word_cost, 0});
+        };
+        lexicon(VBT_LEX_SYSTEM, d.system.params);
+        lexicon(VBT_LEX_USER, d.has_user ? d.user.params : std::vector<WordParam>());
+        w.base[VBT_LEX_UNKNOWN] = (uint32_t)e.size();
+        w.words[VBT_LEX_UNKNOWN] = (uint32_t)d.unk_entries.size();
+        for (const Entry& u : d.unk_entries)  // (word id = row index; the ids and the cost as fill_token takes them)
+            e.push_back(DevWordParam{(uint16_t)(u.left_right & 0xFFFF), (uint16_t)(u.left_right >> 16), (int16_t)(uint16_t)u.cost, 0});
+        e.push_back(DevWordParam{0, 0, 0, 0});
+        HIP_CHECK(hipSetDevice(device_));
+        void* d_e = nullptr;
+        try {
+            HIP_CHECK(hipMalloc(&d_e, e.size() * sizeof(DevWordParam)));
+            HIP_CHECK(hipMemcpy(d_e, e.data(), e.size() * sizeof(DevWordParam), hipMemcpyHostToDevice));
+            HIP_CHECK(hipDeviceSynchronize());  // (the copy has landed before a kernel of any stream reads the table)
+        } catch (...) {
+            if (d_e) (void)hipFree(d_e);
+            throw;
+        }
+        w.e = static_cast<const DevWordParam*>(d_e);
+        wparam_alloc_ = d_e;
+        wparam_ = w;
+    });
+    return wparam_;
 }
 
 double Tokenizer::candidates_per_byte() const {
@@ -502,6 +541,7 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
     last_stream = stream_;
     has_run = true;
     mecab_ran = mecab;
+    detail_ran = detail;
     HIP_CHECK(hipMemsetAsync(d_ctrl, 0, (kCtrlWords + (size_t)kBlockCtrlWords) * 4, stream));  // ctrl + cctrl
     if (packed_slot && n > packed_max_s) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch has more sentences than the packed output slot holds");
     if (n == 0) {
@@ -516,6 +556,12 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
             BatchArgs a{};
             a.ctrl = d_ctrl;
             kern::mecab_lines(stream, a, tok.feature_table(), 0, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, false);
+            HIP_CHECK(hipGetLastError());
+        }
+        if (detail) {
+            BatchArgs a{};
+            a.ctrl = d_ctrl;
+            kern::detail_lines(stream, a, tok.feature_table(), tok.word_param_table(), 0, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, false);
             HIP_CHECK(hipGetLastError());
         }
         return;
@@ -730,10 +776,11 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
         // unless the batch is huge or the caller packs later and wants the grand total first)
         const bool scan_kernel = defer_pack || n_tiles > 2048 || env_u32("VBT_PACK_SCAN", 0);
         // (wakati mode: the lines are rendered from the staging regions; the records are packed only for a caller who wants both)
-        // (MeCab mode likewise; one text mode at a time)
-        const bool records = mecab ? mecab_keep : !wakati || wakati_keep;
+        // (MeCab and detail mode likewise; one text mode at a time)
+        const bool records = detail ? detail_keep : mecab ? mecab_keep : !wakati || wakati_keep;
         if (wakati) kern::wakati_lines(stream, a, n_tiles, d_line_len, d_wakati_tiles, d_line_off, d_wakati, wakati_cap, !records);
         if (mecab) kern::mecab_lines(stream, a, tok.feature_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, !records);
+        if (detail) kern::detail_lines(stream, a, tok.feature_table(), tok.word_param_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, !records);
         if (records && scan_kernel) kern::tok_tile_scan(stream, a, d_tile_sums, n_tiles);
         if (records && !defer_pack) kern::compact_tokens(stream, a, d_tile_sums, n_tiles, scan_kernel ? 1u : 0u);
         last_args = a;
@@ -792,6 +839,7 @@ void Workspace::text_mode_buffers() {
 
 void Workspace::set_wakati(bool on, bool keep_records, uint64_t cap_limit) {
     if (on && mecab) throw Error(VBT_ERR_INVALID_ARGUMENT, "wakati mode: the workspace is in MeCab mode (one text mode at a time)");
+    if (on && detail) throw Error(VBT_ERR_INVALID_ARGUMENT, "wakati mode: the workspace is in detail mode (one text mode at a time)");
     if (on && !d_wakati) {
         HIP_CHECK(hipSetDevice(tok.device()));
         const uint64_t ns = std::max<uint64_t>(max_sentences, 1), cap = 2 * max_bytes + ns;  // bytes + tokens (<= bytes) + a byte per sentence
@@ -813,45 +861,66 @@ void Workspace::set_wakati(bool on, bool keep_records, uint64_t cap_limit) {
     }
 }
 
+// the output buffer and the line lengths of MeCab and detail mode (exclusive modes: one allocation serves both)
+void Workspace::text_out_buffer(uint64_t cap_bytes) {
+    HIP_CHECK(hipSetDevice(tok.device()));
+    text_mode_buffers();
+    if (!d_mecab_len) {
+        void* p = nullptr;
+        HIP_CHECK(hipMalloc(&p, std::max<uint64_t>(max_sentences, 1) * 8));
+        pipe_allocs.push_back(p);
+        d_mecab_len = static_cast<uint64_t*>(p);
+    }
+    if (cap_bytes > mecab_alloc) {  // a larger buffer: the new one first (a failure leaves the old one in place), then the old one goes
+        void* p = nullptr;
+        HIP_CHECK(hipMalloc(&p, ((cap_bytes + 3) & ~3ull) + kWakatiPad));
+        if (d_mecab) {
+            if (has_run) HIP_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(last_stream)));  // (a render may still be writing it)
+            pipe_allocs.erase(std::find(pipe_allocs.begin(), pipe_allocs.end(), static_cast<void*>(d_mecab)));
+            (void)hipFree(d_mecab);
+        }
+        pipe_allocs.push_back(p);
+        d_mecab = static_cast<uint8_t*>(p);
+        mecab_alloc = cap_bytes;
+    }
+    mecab_cap = cap_bytes;
+}
+
 void Workspace::set_mecab(bool on, bool keep_records, uint64_t cap_bytes) {
     if (on && wakati) throw Error(VBT_ERR_INVALID_ARGUMENT, "MeCab mode: the workspace is in wakati mode (one text mode at a time)");
+    if (on && detail) throw Error(VBT_ERR_INVALID_ARGUMENT, "MeCab mode: the workspace is in detail mode (one text mode at a time)");
     if (on && cap_bytes == 0) throw Error(VBT_ERR_INVALID_ARGUMENT, "MeCab mode: cap_bytes must be > 0 (the input does not bound this output: the caller names the capacity)");
     if (on) {
         (void)tok.feature_table();  // uploaded by the first workspace that asks
-        HIP_CHECK(hipSetDevice(tok.device()));
-        text_mode_buffers();
-        if (!d_mecab_len) {
-            void* p = nullptr;
-            HIP_CHECK(hipMalloc(&p, std::max<uint64_t>(max_sentences, 1) * 8));
-            pipe_allocs.push_back(p);
-            d_mecab_len = static_cast<uint64_t*>(p);
-        }
-        if (cap_bytes > mecab_alloc) {  // a larger buffer: the new one first (a failure leaves the old one in place), then the old one goes
-            void* p = nullptr;
-            HIP_CHECK(hipMalloc(&p, ((cap_bytes + 3) & ~3ull) + kWakatiPad));
-            if (d_mecab) {
-                if (has_run) HIP_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(last_stream)));  // (a render may still be writing it)
-                pipe_allocs.erase(std::find(pipe_allocs.begin(), pipe_allocs.end(), static_cast<void*>(d_mecab)));
-                (void)hipFree(d_mecab);
-            }
-            pipe_allocs.push_back(p);
-            d_mecab = static_cast<uint8_t*>(p);
-            mecab_alloc = cap_bytes;
-        }
-        mecab_cap = cap_bytes;
+        text_out_buffer(cap_bytes);
     }
     mecab = on;
     mecab_keep = on && keep_records;
 }
 
+void Workspace::set_detail(bool on, bool keep_records, uint64_t cap_bytes) {
+    if (on && wakati) throw Error(VBT_ERR_INVALID_ARGUMENT, "detail mode: the workspace is in wakati mode (one text mode at a time)");
+    if (on && mecab) throw Error(VBT_ERR_INVALID_ARGUMENT, "detail mode: the workspace is in MeCab mode (one text mode at a time)");
+    if (on && cap_bytes == 0) throw Error(VBT_ERR_INVALID_ARGUMENT, "detail mode: cap_bytes must be > 0 (the input does not bound this output: the caller names the capacity)");
+    if (on) {
+        (void)tok.feature_table();  // both uploaded by the first workspace that asks
+        (void)tok.word_param_table();
+        text_out_buffer(cap_bytes);
+    }
+    detail = on;
+    detail_keep = on && keep_records;
+}
+
 void Workspace::render_text_again(void* stream_) {
-    if (!mecab || !mecab_ran) throw Error(VBT_ERR_INVALID_STATE, "render_text_again: the last run() of this workspace was not in MeCab mode");
+    const bool as_mecab = mecab && mecab_ran, as_detail = detail && detail_ran;
+    if (!as_mecab && !as_detail) throw Error(VBT_ERR_INVALID_STATE, "render_text_again: the last run() of this workspace was not in MeCab or detail mode");
     HIP_CHECK(hipSetDevice(tok.device()));
     last_stream = stream_;
     BatchArgs a = last_args;
     if (last_n == 0) { a = BatchArgs{}; a.ctrl = d_ctrl; }
-    kern::mecab_render_again(reinterpret_cast<hipStream_t>(stream_), a, tok.feature_table(), (uint32_t)((last_n + kScanTile - 1) / kScanTile), d_mecab_len,
-                             d_wakati_tiles, d_line_off, d_mecab, mecab_cap);
+    const uint32_t n_tiles = (uint32_t)((last_n + kScanTile - 1) / kScanTile);
+    if (as_mecab) kern::mecab_render_again(reinterpret_cast<hipStream_t>(stream_), a, tok.feature_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap);
+    else kern::detail_render_again(reinterpret_cast<hipStream_t>(stream_), a, tok.feature_table(), tok.word_param_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -120,8 +120,8 @@ constexpr int kProfSlots = 256;  // the counters are spread over this many copie
 constexpr int kProfWords = 12;   // kProfPhases cycle totals, sentences, lattice steps, lattice passes, candidates
 constexpr int kProfPhases = 8;  // decode, count, fill, end lists, pre-pass, gather, recurrence, emit
 // kErrOffsets / kErrUtf8 are set by validate_batch; the batch is then skipped (no kernel touches the per-sentence regions)
-// kErrWakatiCap: the "text output capacity" flag of BOTH text modes: a line of the wakati output (wakati_render) or of the MeCab-format
-// output (mecab_render; also a line of 4 GiB and more) would have ended beyond the output buffer; the line is not written
+// kErrWakatiCap: the "text output capacity" flag of all three text modes: a line of the wakati output (wakati_render) or of the MeCab-format
+// or detail output (mecab_render, detail_render; also a line of 4 GiB and more) would have ended beyond the output buffer; the line is not written
 enum DevError { kErrTokCap = 1, kErrScratch = 2, kErrTooLong = 4, kErrOffsets = 8, kErrUtf8 = 16, kErrWakatiCap = 32, kErrFatal = kErrOffsets | kErrUtf8 };
 
 // The feature strings of the three lexicons (system, user, unknown) flat on the host: one blob per lexicon + a u32 offset per word id
@@ -136,6 +136,18 @@ struct FlatFeatures { std::vector<uint32_t> off; std::vector<char> blob; };
 struct DevFeatures {
     const uint8_t* blob;
     const uint32_t* off;
+    uint32_t base[3], words[3];
+};
+
+// The per-word parameters a detail line prints (tokenize/src/main.rs:108-123), for detail.hip: one 8-byte entry per word -- system,
+// user, then unknown lexicon, back to back + one closing entry of zeros (entry base[lex] + 0 of an EMPTY last lexicon is inside the
+// array) -- indexed as DevFeatures::off is, with base[] / words[] of its own (off[] has a terminator per lexicon, this array none).
+// left_id / right_id are the DICTIONARY's connection ids (Lexicon::params, unk_entries: what fill_token reads), not the device ids
+// of a DevImage's entry arrays, which the calibration renumbers: one table serves every image, like the feature table.
+struct DevWordParam { uint16_t left_id, right_id; int16_t word_cost; uint16_t spare; };
+static_assert(sizeof(DevWordParam) == 8, "one 8-byte load per token");
+struct DevWordParams {
+    const DevWordParam* e;
     uint32_t base[3], words[3];
 };
 
@@ -200,6 +212,10 @@ class Tokenizer {
     // that never renders MeCab text pays no HBM -- and freed with the tokenizer.  4 GiB of feature strings and more in all:
     // VBT_ERR_UNSUPPORTED.  A failed upload leaves nothing allocated and is tried again by the next call.
     const DevFeatures& feature_table() const;
+    // The word-parameter table of detail mode, likewise under a call_once of its own: uploaded by the first workspace that enables
+    // detail mode (a tokenizer that renders only MeCab or wakati text pays nothing), freed with the tokenizer; a failed upload leaves
+    // nothing allocated and is tried again by the next call.
+    const DevWordParams& word_param_table() const;
 
   private:
     void upload_lexicon(const Lexicon& lx, DevLexicon& out);
@@ -234,6 +250,9 @@ class Tokenizer {
     mutable std::once_flag flat_once_, feat_once_;
     mutable DevFeatures feat_{};
     mutable void* feat_allocs_[2] = {nullptr, nullptr};
+    mutable std::once_flag wparam_once_;
+    mutable DevWordParams wparam_{};
+    mutable void* wparam_alloc_ = nullptr;
 };
 
 class Workspace {
@@ -273,8 +292,15 @@ class Workspace {
     // Valid after a run() in MeCab mode until the next run(), with the batch's text and offsets still in place: takes the capacity
     // flag back on `stream` and renders the lines once more (mecab_render alone: the staging regions, the line lengths and the tile
     // prefix of the run still hold) -- after set_mecab with a larger capacity, growing costs one render, not a second tokenisation.
+    // (after a run() in detail mode: detail_render alone, likewise)
     void render_text_again(void* stream);
     bool mecab = false, mecab_keep = false;
+    // Detail output mode (detail.hip; tokenize/src/main.rs:108-123): as MeCab mode, every token's line extended by "\tlex_type=..
+    // \tleft_id=.. \tright_id=.. \tword_cost=.. \ttotal_cost=..".  The modes are exclusive, so this one uses MeCab mode's buffers
+    // (d_mecab, the line lengths, d_line_off), capacity protocol and pad; render_text_again serves whichever of the two the last
+    // run() used.  One text mode at a time, among the three.
+    void set_detail(bool on, bool keep_records, uint64_t cap_bytes);
+    bool detail = false, detail_keep = false;
     uint8_t* d_mecab = nullptr;
     uint64_t mecab_cap = 0, mecab_alloc = 0;  // bytes the kernels may use / bytes the buffer holds in front of its pad
     void* packed_slot = nullptr;
@@ -330,9 +356,11 @@ class Workspace {
     uint64_t* d_wakati_tiles = nullptr;
     uint64_t* d_mecab_len = nullptr;     // MeCab mode: bytes per line (d_wakati_tiles and d_line_off serve both text modes)
     bool mecab_ran = false;              // the last run() rendered MeCab text: render_text_again may follow
+    bool detail_ran = false;             // ... or detail text
 
   private:
     void text_mode_buffers();  // d_wakati_tiles, d_line_off: allocated by the text mode that is enabled first
+    void text_out_buffer(uint64_t cap_bytes);  // d_mecab_len, d_mecab of at least cap_bytes (+ pad): MeCab and detail mode
     void release();  // frees every device allocation, stream and event (also on a constructor failure)
 };
 

@@ -1,4 +1,4 @@
-// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip, wakati.hip, mecab.hip), as plain
+// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip, wakati.hip, mecab.hip, detail.hip), as plain
 // functions the host side (engine.hip: Tokenizer, Workspace) calls.  Every launcher enqueues on `stream` and returns.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -74,6 +74,16 @@ void mecab_lines(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, u
                  uint8_t* out, uint64_t out_cap, bool count_tokens);
 void mecab_render_again(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, uint32_t n_tiles, const uint64_t* line_len, const uint64_t* tile_bytes,
                         uint64_t* line_off, uint8_t* out, uint64_t out_cap);
+
+// ---- detail.hip: the detail text of a batch (tokenize/src/main.rs:108-123: per token "surface \t feature \tlex_type=.. \tleft_id=..
+// \tright_id=.. \tword_cost=.. \ttotal_cost=.. \n", "EOS\n" per sentence) from the staging regions, the feature table `f` and the
+// word-parameter table `w`.  detail_plan -> text_tile_scan -> detail_render, with the buffers, the capacity rule and the flag of
+// mecab_lines; detail_render_again as mecab_render_again.
+uint32_t detail_round();  // tokens per LDS round of detail_render
+void detail_lines(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, const DevWordParams& w, uint32_t n_tiles, uint64_t* line_len, uint64_t* tile_bytes,
+                  uint64_t* line_off, uint8_t* out, uint64_t out_cap, bool count_tokens);
+void detail_render_again(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, const DevWordParams& w, uint32_t n_tiles, const uint64_t* line_len,
+                         const uint64_t* tile_bytes, uint64_t* line_off, uint8_t* out, uint64_t out_cap);
 
 // the calibration sample (Tokenizer::maybe_calibrate): up to `want` sentences spread evenly over the batch, copied into s_text / s_offs
 // (s_offs[0 .. k], k = info[0] = the sentences whose text fits cap_bytes; s_src: want words of scratch), on `stream`

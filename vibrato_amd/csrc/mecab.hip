@@ -16,8 +16,8 @@
 // everything else (surfaces, '\t', '\n', token borders, "EOS\n", the ragged ends of the span) is put together byte by byte.  Full
 // dwords leave as one aligned 32-bit store, only the ragged first and last dword of a span as byte stores.  Nothing is sized by the
 // longest sentence or feature: more tokens than a round loop over rounds, more dwords than 64 loop over the lanes.
-// (The piece table is where a detail mode would extend: its five decimal fields are further pieces of a token's span.)
-#include "device_common.hpp"
+// (detail.hip is this scheme with a longer piece table: the decimal fields of a detail line are further pieces of a token's span.)
+#include "text_pieces.hpp"  // Piece, load_piece, wave_sum64: shared with detail.hip
 
 namespace vbt {
 namespace {
@@ -27,29 +27,6 @@ constexpr uint32_t kMecabRound = VBT_MECAB_ROUND;
 static_assert(kScanTile <= kMecabBlock && kScanTile % kMecabWaves == 0 && kScanTile % 64 == 0, "a thread per sentence for the tile's scan");
 static_assert(kMecabRound % 64 == 0, "a round is loaded 64 tokens at a time");
 static_assert(kMecabWaves * (4 * kMecabRound + 1) * 4 + (kScanTile + 1 + kScanTile / 64) * 8 <= 65536, "the piece tables and the tile's offsets within 64 KiB of LDS");
-
-struct Piece { uint32_t start, end, feat, feat_len; };  // of one token: its surface in the sentence, its feature in the blob
-
-// {start_byte, end_byte, word_idx} of record k of the staging region that starts at `slot` (words 2-4 of the 24-byte record) and the
-// two offsets of its feature.  A word index outside the table -- the device wrote the record itself, so this is memory safety, not
-// an input that is served -- is clamped to the table: a lexicon tag above 2 to the unknown lexicon, an id to the lexicon's last.
-// (off[] ends with one entry more than the lexicons have, so that an EMPTY lexicon's entry 0 and 1 are inside it as well.)
-__device__ __forceinline__ Piece load_piece(const BatchArgs& A, const DevFeatures& F, size_t slot, uint32_t k) {
-    const uint32_t* rec = reinterpret_cast<const uint32_t*>(A.tok_stage) + 6 * (slot + k);
-    const uint2 se = *reinterpret_cast<const uint2*>(rec + 2);
-    const uint32_t widx = rec[4];
-    const uint32_t lex = min(widx >> 30, 2u), wid = widx & 0x3FFFFFFFu;
-    const uint32_t nw = lex == 0 ? F.words[0] : lex == 1 ? F.words[1] : F.words[2];
-    const uint32_t base = lex == 0 ? F.base[0] : lex == 1 ? F.base[1] : F.base[2];
-    const uint32_t i = base + min(wid, nw ? nw - 1u : 0u);
-    const uint32_t f0 = F.off[i], f1 = F.off[i + 1];
-    return Piece{se.x, se.y, f0, f1 - f0};
-}
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {  // in three 24-bit limbs (64 of them add up inside 32 bits)
-    const uint64_t a = wave_sum((uint32_t)v & 0xFFFFFFu), b = wave_sum((uint32_t)(v >> 24) & 0xFFFFFFu), c = wave_sum((uint32_t)(v >> 48));
-    return a + (b << 24) + (c << 48);
-}
 
 // line_len[s] = per token its surface + '\t' + its feature + '\n', then "EOS\n"
 __global__ void __launch_bounds__(kMecabBlock) mecab_plan(BatchArgs A, DevFeatures F, uint64_t* __restrict__ line_len, uint64_t* __restrict__ tile_bytes) {
