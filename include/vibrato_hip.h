@@ -294,6 +294,28 @@ VBT_API int vbt_tokenize_mecab(const vbt_tokenizer* tok, const uint8_t* text, co
  * ids printed are the dictionary's, from a word-parameter table of the device image uploaded at the first call. */
 VBT_API int vbt_tokenize_detail(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
                                 char** out, size_t* len, uint64_t* line_off);
+/* Raw bytes in -> sentences out, the lines cut ON THE DEVICE (split.hip) with the semantics of BufRead::lines(), which the
+ * reference's CLI reads its input with (tokenize/src/main.rs:78-80): a line ends at '\n'; ONE '\r' directly in front of that '\n' goes
+ * with it; every other '\r' is text (a lone one, the first of "\r\r\n", the last byte of an unterminated last line); an empty line is
+ * a sentence of length 0; a trailing '\n' opens no further sentence.  What follows the last '\n' is the tail: with final != 0 a tail
+ * that is not empty is the last sentence and *consumed = len; with final == 0 the tail is left to the caller -- *consumed is the index
+ * behind the last '\n' (0 and *n = 0 when there is none), and the next call starts with raw + *consumed in front of what was read
+ * since.  *text = the sentences back to back without their terminators, *offsets = n + 1 byte offsets into it (offsets[0] = 0): what
+ * vbt_tokenize_batch and -- on the device -- vbt_tokenize_batch_device take.  Both are released ONLY with vbt_free.  The bytes are
+ * not checked for UTF-8 here (the tokenize calls do that).  Three kernels over tiles of VBT_SPLIT_TILE bytes -- count, scan of the
+ * tiles' counts, scatter -- none of which waits for another workgroup.  len >= 4 GiB: VBT_ERR_INVALID_ARGUMENT; a multi-device
+ * tokenizer: VBT_ERR_UNSUPPORTED; len == 0 launches nothing. */
+#define VBT_SPLIT_TILE 16384
+VBT_API int vbt_split_lines(const vbt_tokenizer* tok, const uint8_t* raw, size_t len, int final, uint8_t** text,
+                            uint64_t** offsets /* n + 1 */, uint64_t* n, size_t* consumed);
+/* Raw bytes in -> rendered text out (mode = VBT_FORMAT_MECAB | VBT_FORMAT_WAKATI | VBT_FORMAT_DETAIL): vbt_split_lines in front of
+ * vbt_tokenize_mecab / _wakati / _detail without the sentences ever visiting the host -- the raw bytes go to the device in one copy,
+ * 16 bytes come back ({n, consumed, bytes of text}: the call picks its pooled workspace by them), the scatter kernel writes the
+ * text and the offsets where the tokenizer reads them, and everything behind is the text call of that mode (capacity protocol, at
+ * most one re-render, *out released ONLY with vbt_free).  *n = sentences rendered, *consumed as vbt_split_lines.  Errors as there, and
+ * VBT_ERR_UTF8 naming the line (counted from 0 within this call) for text that is not UTF-8. */
+VBT_API int vbt_tokenize_stream(const vbt_tokenizer* tok, int mode, const uint8_t* raw, size_t len, int final, char** out,
+                                size_t* out_len, uint64_t* n, size_t* consumed);
 
 /* ---- Device-resident API (zero-copy; what bench.py times) ------------------------ */
 

@@ -152,6 +152,12 @@ extern "C" {
                               line_off: *mut u64) -> c_int;
     pub fn vbt_tokenize_detail(tok: *const vbt_tokenizer, text: *const u8, offsets: *const u64, n: u64, out: *mut *mut c_char, len: *mut usize,
                                line_off: *mut u64) -> c_int;
+    /// Raw bytes -> sentences, the lines cut on the device (`BufRead::lines()` semantics); `*text` / `*offsets` released with `vbt_free`.
+    pub fn vbt_split_lines(tok: *const vbt_tokenizer, raw: *const u8, len: usize, is_final: c_int, text: *mut *mut u8, offsets: *mut *mut u64,
+                           n: *mut u64, consumed: *mut usize) -> c_int;
+    /// Raw bytes -> rendered text (`mode`: `VBT_FORMAT_*`), the lines cut on the device; `*out` released with `vbt_free`.
+    pub fn vbt_tokenize_stream(tok: *const vbt_tokenizer, mode: c_int, raw: *const u8, len: usize, is_final: c_int, out: *mut *mut c_char,
+                               out_len: *mut usize, n: *mut u64, consumed: *mut usize) -> c_int;
 
     // ---- Device-resident API
     pub fn vbt_workspace_new(tok: *const vbt_tokenizer, max_sentences: u64, max_bytes: u64, out: *mut *mut vbt_workspace) -> c_int;

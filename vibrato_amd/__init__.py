@@ -4,7 +4,7 @@ built into lib/libvibrato_hip.so); this package is the thin host mirror of vibra
 Dictionary / Tokenizer / Worker / Token API."""
 from .api import (Batch, Dictionary, SystemDictionaryBuilder, Token, Tokenizer, VibratoError, Worker,  # noqa: F401
                   Workspace, TOKEN_DTYPE, LEX_NAMES, compute_connid_probs)
-from ._native import DETAIL_ROUND, MECAB_ROUND, WAKATI_ROUND  # noqa: F401
+from ._native import DETAIL_ROUND, MECAB_ROUND, SPLIT_TILE, WAKATI_ROUND  # noqa: F401
 
-__all__ = ["DETAIL_ROUND", "MECAB_ROUND", "WAKATI_ROUND", "Batch", "Dictionary", "SystemDictionaryBuilder", "Token", "Tokenizer", "VibratoError", "Worker",
+__all__ = ["DETAIL_ROUND", "MECAB_ROUND", "SPLIT_TILE", "WAKATI_ROUND", "Batch", "Dictionary", "SystemDictionaryBuilder", "Token", "Tokenizer", "VibratoError", "Worker",
            "Workspace", "TOKEN_DTYPE", "LEX_NAMES", "compute_connid_probs"]

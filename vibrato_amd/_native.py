@@ -43,6 +43,7 @@ class CallStats(C.Structure):
 WAKATI_ROUND = 256  # VBT_WAKATI_ROUND of include/vibrato_hip.h: tokens per LDS round of the wakati render kernel
 MECAB_ROUND = 128   # VBT_MECAB_ROUND: the same of the MeCab-format render kernel
 DETAIL_ROUND = 64   # VBT_DETAIL_ROUND: the same of the detail render kernel
+SPLIT_TILE = 16384  # VBT_SPLIT_TILE: bytes per workgroup of the line-cutting kernels
 
 # name -> (restype, argtypes); also the list of symbols include/vibrato_hip.h declares.
 _vp, _cp, _sz, _u32, _u64, _int = C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
@@ -105,6 +106,8 @@ SIGNATURES = {
     "vbt_tokenize_wakati": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
     "vbt_tokenize_mecab": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
     "vbt_tokenize_detail": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
+    "vbt_split_lines": (_int, [_vp, _vp, _sz, _int, _PP, _PP, C.POINTER(_u64), C.POINTER(_sz)]),
+    "vbt_tokenize_stream": (_int, [_vp, _int, _vp, _sz, _int, _PP, C.POINTER(_sz), C.POINTER(_u64), C.POINTER(_sz)]),
     "vbt_workspace_new": (_int, [_vp, _u64, _u64, _PP]),
     "vbt_workspace_free": (None, [_vp]),
     "vbt_tokenize_batch_device": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),

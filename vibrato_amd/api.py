@@ -369,6 +369,36 @@ class Tokenizer:
             N.lib().vbt_free(p)
         return (out, line_off) if with_offsets else out
 
+    def split_lines(self, raw, final=True):
+        """Raw bytes -> (text, np.uint64 offsets[n + 1], consumed): the lines of `raw` cut on the device (vbt_split_lines) as
+        BufRead::lines() cuts them -- "\n" and "\r\n" end a line, any other "\r" is text, empty lines are sentences.  `text` holds the
+        sentences back to back, what tokenize_batch(text=, offsets=) and its siblings take.  final=False: the bytes behind the last
+        "\n" are not a sentence yet; raw[consumed:] goes in front of the next block.  Single-device tokenizers only."""
+        raw = bytes(raw)
+        pt, po, n, used = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_size_t()
+        N.check(N.lib().vbt_split_lines(self._handle(), raw or None, len(raw), int(bool(final)), C.byref(pt), C.byref(po), C.byref(n), C.byref(used)))
+        try:
+            offsets = np.frombuffer(C.string_at(po, 8 * (n.value + 1)), dtype=np.uint64)
+            text = C.string_at(pt, int(offsets[-1]))
+        finally:
+            N.lib().vbt_free(pt)
+            N.lib().vbt_free(po)
+        return text, offsets, used.value
+
+    def tokenize_stream(self, raw, mode="mecab", final=True):
+        """Raw bytes -> (rendered text, n, consumed): split_lines in front of tokenize_mecab / tokenize_wakati / tokenize_detail
+        (`mode`) in ONE call (vbt_tokenize_stream) -- the lines are cut on the device and written where the tokenizer reads them.
+        A reader feeds blocks with final=False, carries raw[consumed:] over, and ends with one final=True call."""
+        raw = bytes(raw)
+        p, ln, n, used = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_size_t()
+        N.check(N.lib().vbt_tokenize_stream(self._handle(), {"mecab": 0, "wakati": 1, "detail": 2}[mode], raw or None, len(raw), int(bool(final)), C.byref(p), C.byref(ln),
+                                            C.byref(n), C.byref(used)))
+        try:
+            out = C.string_at(p, ln.value)
+        finally:
+            N.lib().vbt_free(p)
+        return out, n.value, used.value
+
     def tokenize_lines(self, lines, batch_bytes=16 << 20, batch_lines=100000):
         """The per-line loop of the reference's callers (tokenize/src/main.rs:78-95) over an iterable of lines, batched behind the
         scenes: lines are collected until `batch_bytes` of text (or `batch_lines` lines) are in hand, tokenized as ONE device batch and

@@ -53,6 +53,18 @@ struct PooledWorkspace {
     }
 };
 
+// Plain device memory with a stream of its own, recycled between the calls that start from raw bytes (vbt_split_lines,
+// vbt_tokenize_stream): the raw buffer and the scratch of the line-cutting kernels, whose size is known before the workspace's is.
+struct DevBlock {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipStream_t stream = nullptr;
+    ~DevBlock() {
+        if (p) (void)hipFree(p);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
 // Page-locked host memory recycled between batches: a batch's copy of the text and its results live in pinned blocks, so
 // both directions are true asynchronous DMA on the workspace's stream (pageable copies are staged by the runtime and
 // block), and hipHostMalloc (~ms per block) is off the steady-state path.
@@ -216,6 +228,7 @@ struct Replica {
     std::vector<int> near_cpus;                          // CPUs of the device's NUMA node (empty: unknown)
     std::unique_ptr<Tokenizer> t;
     std::vector<std::unique_ptr<PooledWorkspace>> pool;  // idle workspaces (guarded by the tokenizer's pool_mu)
+    std::vector<std::unique_ptr<DevBlock>> dev_pool;     // idle device blocks of the raw-byte entry points (likewise)
     std::unique_ptr<Sdma> sdma;                          // device -> pinned-host copies on the DMA engines (created at the first host batch)
     uint64_t dev_budget = 0;                             // bytes of idle workspaces this device keeps (VBT_POOL_MAX_MB, default a quarter of its memory)
 };
@@ -506,6 +519,48 @@ void pool_give(vbt_tokenizer* tok, Replica& rep, std::unique_ptr<PooledWorkspace
         }
     }
     if (drop) { (void)hipSetDevice(rep.t->device()); drop.reset(); }
+}
+
+// Device blocks of the raw-byte entry points: the smallest idle one that holds the request, else a new one (capacity rounded up to a
+// power of two); at most kDevPoolIdle stay idle per device, the smallest is dropped first.  (Next to a workspace's ~400 bytes per
+// byte of text they do not count against the device budget.)
+constexpr size_t kDevPoolIdle = 4;
+std::unique_ptr<DevBlock> dev_take(vbt_tokenizer* tok, Replica& rep, size_t bytes) {
+    {
+        std::lock_guard<std::mutex> g(tok->pool_mu);
+        size_t best = rep.dev_pool.size();
+        for (size_t i = 0; i < rep.dev_pool.size(); ++i)
+            if (rep.dev_pool[i]->cap >= bytes && (best == rep.dev_pool.size() || rep.dev_pool[i]->cap < rep.dev_pool[best]->cap)) best = i;
+        if (best != rep.dev_pool.size()) {
+            auto b = std::move(rep.dev_pool[best]);
+            rep.dev_pool.erase(rep.dev_pool.begin() + (long)best);
+            return b;
+        }
+    }
+    HIPX(hipSetDevice(rep.t->device()));
+    auto b = std::make_unique<DevBlock>();
+    b->cap = round_up_pow2(bytes, 1 << 16);
+    HIPX(hipMalloc(&b->p, b->cap));
+    HIPX(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    return b;
+}
+
+void dev_give(vbt_tokenizer* tok, Replica& rep, std::unique_ptr<DevBlock> b) {
+    if (!b) return;
+    (void)hipSetDevice(rep.t->device());
+    (void)hipStreamSynchronize(b->stream);  // (nothing of the call that held it is still reading it)
+    std::unique_ptr<DevBlock> drop;  // freed outside the lock
+    {
+        std::lock_guard<std::mutex> g(tok->pool_mu);
+        rep.dev_pool.push_back(std::move(b));
+        if (rep.dev_pool.size() > kDevPoolIdle) {
+            size_t smallest = 0;
+            for (size_t i = 1; i < rep.dev_pool.size(); ++i)
+                if (rep.dev_pool[i]->cap < rep.dev_pool[smallest]->cap) smallest = i;
+            drop = std::move(rep.dev_pool[smallest]);
+            rep.dev_pool.erase(rep.dev_pool.begin() + (long)smallest);
+        }
+    }
 }
 
 // Buffers the library hands out and vbt_free takes back (vbt_batch_format's text, vbt_dict_write's bytes).  A 16-byte header in
@@ -1502,6 +1557,106 @@ int vbt_tokenize_batch(const vbt_tokenizer* tok_, const uint8_t* text, const uin
 // is rendered once more into a buffer of the exact size the device reported (Workspace::render_text_again), not tokenized again.
 // Detail text (detail.hip; tokenize/src/main.rs:108-123) is MeCab format's protocol with a ratio and an environment override of its own.
 enum TextMode { kTextWakati, kTextMecab, kTextDetail };
+
+// What a text call holds while it runs: the pinned block, the device block of a call that starts from raw bytes (vbt_tokenize_stream)
+// and the workspace go back to their pools on every path, the workspace in record mode.
+struct TextCall {
+    vbt_tokenizer* tok;
+    Replica& rep;
+    std::unique_ptr<PinnedBlock> blk;
+    std::unique_ptr<PooledWorkspace> p;
+    std::unique_ptr<DevBlock> raw, cut;  // raw bytes + split scratch; vbt_split_lines: the sentences it copies out
+    void* result = nullptr;  // handed to the caller at the end, released here on a failure
+    TextCall(vbt_tokenizer* t, Replica& r) : tok(t), rep(r) {}
+    ~TextCall() {
+        if (p) {
+            (void)hipSetDevice(rep.t->device());
+            (void)hipStreamSynchronize(p->stream);
+            p->ws->set_wakati(false, false);
+            p->ws->set_mecab(false, false, 0);
+            p->ws->set_detail(false, false, 0);
+            pool_give(tok, rep, std::move(p));
+        }
+        dev_give(tok, rep, std::move(raw));  // (waits for the block's stream first)
+        dev_give(tok, rep, std::move(cut));
+        host_give(tok, std::move(blk));
+        if (result) out_free(result);
+    }
+};
+
+static void empty_text_result(char** out, size_t* len) {
+    void* p = out_alloc(0);
+    if (!p) throw std::bad_alloc();
+    *out = static_cast<char*>(p); *len = 0;
+}
+
+// The back half of every text call: takes a workspace for n sentences / `bytes` of text, switches the mode on, has `feed` put the
+// text and the offsets into the workspace's d_text / d_off on its stream, runs the batch, follows the capacity protocol and copies
+// exactly the rendered bytes (and the line offsets, when asked for) out.  tail: 16 pinned bytes {tokens u32, error flags u32, total
+// u64}, with n + 1 pinned line offsets behind them when line_off is set.  bad_utf8: throws the VBT_ERR_UTF8 that names the line.
+static void render_text_batch(TextMode mode, vbt_tokenizer* tok, TextCall& h, uint64_t n, uint64_t bytes, uint32_t* tail, uint64_t* line_off, char** out, size_t* len,
+                              const std::function<void(PooledWorkspace&)>& feed, const std::function<void()>& bad_utf8) {
+    const bool mecab = mode != kTextWakati;  // the capacity protocol: MeCab and detail mode
+    const bool detail = mode == kTextDetail;
+    std::atomic<uint32_t>& per_kib = detail ? tok->detail_per_kib : tok->mecab_per_kib;
+    Replica& rep = h.rep;
+    const bool use_sdma = results_by_sdma(tok);
+    uint64_t* total = reinterpret_cast<uint64_t*>(tail + 2);
+    uint64_t* loff = total + 1;
+    tail[0] = tail[1] = 0; *total = 0;
+    HIPX(hipSetDevice(rep.t->device()));
+    h.p = pool_take(tok, rep, n, bytes);
+    PooledWorkspace& p = *h.p;
+    if (mecab) {
+        // first capacity: the running maximum of output bytes per KiB of input + 1/8 + "EOS\n" per sentence; 8 x the input before
+        // any batch has been seen; VBT_MECAB_FIRST_CAP (bytes, read per call: tests, A/B runs) overrides
+        // (detail mode: 16 x, VBT_DETAIL_FIRST_CAP)
+        const uint32_t r = per_kib.load(std::memory_order_relaxed);
+        uint64_t cap = (r ? (bytes * r / 1024) * 9 / 8 : (detail ? 16 : 8) * bytes) + 4 * n;
+        if (const char* e = std::getenv(detail ? "VBT_DETAIL_FIRST_CAP" : "VBT_MECAB_FIRST_CAP")) { const uint64_t v = std::strtoull(e, nullptr, 10); if (v) cap = v; }
+        if (detail) p.ws->set_detail(true, false, cap); else p.ws->set_mecab(true, false, cap);
+    } else {
+        p.ws->set_wakati(true, false);
+    }
+    feed(p);
+    p.ws->run(static_cast<const uint8_t*>(p.d_text), p.d_off, n, bytes, p.stream);
+    HIPX(hipMemcpyAsync(tail, p.ws->d_ctrl, 8, hipMemcpyDeviceToHost, p.stream));
+    HIPX(hipMemcpyAsync(total, p.ws->d_line_off + n, 8, hipMemcpyDeviceToHost, p.stream));
+    HIPX(hipStreamSynchronize(p.stream));
+    if (tail[1] & kErrUtf8) bad_utf8();
+    if (mecab && tail[1] == (uint32_t)kErrWakatiCap) {  // the capacity alone: the exact need is known now -- grow, render once more
+        if (detail) p.ws->set_detail(true, false, *total); else p.ws->set_mecab(true, false, *total);
+        p.ws->render_text_again(p.stream);
+        HIPX(hipMemcpyAsync(tail, p.ws->d_ctrl, 8, hipMemcpyDeviceToHost, p.stream));
+        HIPX(hipStreamSynchronize(p.stream));
+        if (tail[1] & kErrWakatiCap) throw Error(VBT_ERR_DEVICE, "vbt_tokenize_mecab / vbt_tokenize_detail: the text does not fit a buffer of the size the device asked for");
+    }
+    check_device_errors(tail[1]);
+    const size_t out_bytes = (size_t)*total;
+    if (mecab && bytes) {  // bytes of output per KiB of text, rounded up: the largest seen
+        const uint32_t r = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, ((uint64_t)out_bytes * 1024 + bytes - 1) / bytes + 1);
+        uint32_t cur = per_kib.load(std::memory_order_relaxed);
+        while (r > cur && !per_kib.compare_exchange_weak(cur, r, std::memory_order_relaxed)) {}
+    }
+    h.result = pin_out_alloc(out_bytes);
+    const void* src[2] = {mecab ? p.ws->d_mecab : p.ws->d_wakati, p.ws->d_line_off};
+    void* dst[2] = {h.result, loff};
+    const size_t sz[2] = {out_bytes, line_off ? (size_t)(n + 1) * 8 : 0};
+    if (use_sdma) {
+        std::vector<hsa_signal_t> sigs;
+        bool ok = rep.sdma->issue(src, dst, sz, 2, sigs);
+        ok = Sdma::wait(sigs) && ok;
+        if (!ok) throw Error(VBT_ERR_DEVICE, "device -> host copy of the rendered text failed (hsa_amd_memory_async_copy)");
+    } else {
+        for (int k = 0; k < 2; ++k)
+            if (sz[k]) HIPX(hipMemcpyAsync(dst[k], src[k], sz[k], hipMemcpyDeviceToHost, p.stream));
+        HIPX(hipStreamSynchronize(p.stream));
+    }
+    if (line_off) std::memcpy(line_off, loff, (n + 1) * 8);
+    *out = static_cast<char*>(h.result); *len = out_bytes;
+    h.result = nullptr;
+}
+
 static int tokenize_text_on_device(TextMode mode, const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len,
                                    uint64_t* line_off) {
     return guarded([&] {
@@ -1511,108 +1666,124 @@ static int tokenize_text_on_device(TextMode mode, const vbt_tokenizer* tok_, con
             throw Error(VBT_ERR_UNSUPPORTED, mode == kTextDetail  ? "vbt_tokenize_detail: a multi-device tokenizer cannot render detail output (sharded rendering is not implemented)"
                                              : mode == kTextMecab ? "vbt_tokenize_mecab: a multi-device tokenizer cannot render MeCab output (sharded rendering is not implemented)"
                                                                   : "vbt_tokenize_wakati: a multi-device tokenizer cannot render wakati output (sharded rendering is not implemented)");
-        const bool mecab = mode != kTextWakati;  // the capacity protocol: MeCab and detail mode
-        const bool detail = mode == kTextDetail;
-        std::atomic<uint32_t>& per_kib = detail ? tok->detail_per_kib : tok->mecab_per_kib;
         const uint64_t lo = offsets[0];
         for (uint64_t i = 1; i <= n; ++i)
             if (offsets[i] < offsets[i - 1]) throw Error(VBT_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
         const uint64_t bytes = offsets[n] - lo;
         if (bytes >= 0xFFFFFFFFull || n >= 0xFFFFFFFFull) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch too large (split it)");
         if (n == 0) {
-            void* p = out_alloc(0);
-            if (!p) throw std::bad_alloc();
-            *out = static_cast<char*>(p); *len = 0;
+            empty_text_result(out, len);
             if (line_off) line_off[0] = 0;
             return;
         }
-        Replica& rep = *tok->reps[0];
-        const bool use_sdma = results_by_sdma(tok);
-        struct Holder {  // the block and the workspace go back to their pools on every path, the workspace in record mode
-            vbt_tokenizer* tok;
-            Replica& rep;
-            std::unique_ptr<PinnedBlock> blk;
-            std::unique_ptr<PooledWorkspace> p;
-            void* result = nullptr;  // handed to the caller at the end, released here on a failure
-            ~Holder() {
-                if (p) {
-                    (void)hipSetDevice(rep.t->device());
-                    (void)hipStreamSynchronize(p->stream);
-                    p->ws->set_wakati(false, false);
-                    p->ws->set_mecab(false, false, 0);
-                    p->ws->set_detail(false, false, 0);
-                    pool_give(tok, rep, std::move(p));
-                }
-                host_give(tok, std::move(blk));
-                if (result) out_free(result);
-            }
-        } h{tok, rep, nullptr, nullptr};
+        TextCall h(tok, *tok->reps[0]);
         // pinned: [n + 1 rebased offsets][text, padded to 8][{tokens u32, error flags u32}, total u64][n + 1 line offsets]
         const size_t text_end = (n + 1) * 8 + ((bytes + 7) & ~(uint64_t)7);
         h.blk = host_take(tok, text_end + 16 + (n + 1) * 8);
         uint64_t* offs = static_cast<uint64_t*>(h.blk->p);
         uint8_t* txt = reinterpret_cast<uint8_t*>(offs + n + 1);
         uint32_t* tail = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(h.blk->p) + text_end);
-        uint64_t* total = reinterpret_cast<uint64_t*>(tail + 2);
-        uint64_t* loff = total + 1;
         for (uint64_t i = 0; i <= n; ++i) offs[i] = offsets[i] - lo;
         if (bytes) std::memcpy(txt, text + lo, bytes);
-        tail[0] = tail[1] = 0; *total = 0;
-        HIPX(hipSetDevice(rep.t->device()));
-        h.p = pool_take(tok, rep, n, bytes);
-        PooledWorkspace& p = *h.p;
-        if (mecab) {
-            // first capacity: the running maximum of output bytes per KiB of input + 1/8 + "EOS\n" per sentence; 8 x the input before
-            // any batch has been seen; VBT_MECAB_FIRST_CAP (bytes, read per call: tests, A/B runs) overrides
-            // (detail mode: 16 x, VBT_DETAIL_FIRST_CAP)
-            const uint32_t r = per_kib.load(std::memory_order_relaxed);
-            uint64_t cap = (r ? (bytes * r / 1024) * 9 / 8 : (detail ? 16 : 8) * bytes) + 4 * n;
-            if (const char* e = std::getenv(detail ? "VBT_DETAIL_FIRST_CAP" : "VBT_MECAB_FIRST_CAP")) { const uint64_t v = std::strtoull(e, nullptr, 10); if (v) cap = v; }
-            if (detail) p.ws->set_detail(true, false, cap); else p.ws->set_mecab(true, false, cap);
-        } else {
-            p.ws->set_wakati(true, false);
+        render_text_batch(mode, tok, h, n, bytes, tail, line_off, out, len,
+            [&](PooledWorkspace& p) {
+                if (bytes) HIPX(hipMemcpyAsync(p.d_text, txt, bytes, hipMemcpyHostToDevice, p.stream));
+                HIPX(hipMemcpyAsync(p.d_off, offs, (n + 1) * 8, hipMemcpyHostToDevice, p.stream));
+            },
+            [&] {
+                for (uint64_t i = 0; i < n; ++i)
+                    if (!valid_utf8(txt + offs[i], offs[i + 1] - offs[i])) throw Error(VBT_ERR_UTF8, "sentence " + std::to_string(i) + " is not valid UTF-8");
+            });
+    });
+}
+
+// Raw bytes -> sentences cut on the device (split.hip), the front half vbt_split_lines and vbt_tokenize_stream share: the bytes go
+// through the call's pinned block into a pooled device block in ONE copy, the count pass and the scan of its tiles run on that
+// block's stream, and {n, consumed, bytes of text, tail} come back in one 16-byte copy the call waits for.  Pinned block:
+// [raw, padded to 16][SplitInfo][`pinned_behind` bytes of the caller's]; device block: [raw, padded to 16][split scratch].
+struct SplitFront { SplitInfo info; const uint8_t* d_raw; const void* d_scratch; uint8_t* pinned_behind; };
+static SplitFront split_on_device(vbt_tokenizer* tok, TextCall& h, const uint8_t* raw, size_t len, bool final, size_t pinned_behind) {
+    const size_t padded = (len + 15) & ~(size_t)15;
+    h.blk = host_take(tok, padded + sizeof(SplitInfo) + pinned_behind);
+    uint8_t* pin = static_cast<uint8_t*>(h.blk->p);
+    SplitInfo* info = reinterpret_cast<SplitInfo*>(pin + padded);
+    std::memcpy(pin, raw, len);
+    *info = SplitInfo{};
+    HIPX(hipSetDevice(h.rep.t->device()));
+    h.raw = dev_take(tok, h.rep, padded + split_scratch_bytes(len));
+    uint8_t* d_raw = static_cast<uint8_t*>(h.raw->p);
+    HIPX(hipMemcpyAsync(d_raw, pin, len, hipMemcpyHostToDevice, h.raw->stream));
+    split_count(d_raw, len, final, d_raw + padded, h.raw->stream);
+    HIPX(hipMemcpyAsync(info, d_raw + padded, sizeof(SplitInfo), hipMemcpyDeviceToHost, h.raw->stream));
+    HIPX(hipStreamSynchronize(h.raw->stream));
+    if (info->consumed > len || info->text_bytes > info->consumed || info->n > len + 1) throw Error(VBT_ERR_DEVICE, "the device's line counts do not fit the buffer");
+    return SplitFront{*info, d_raw, d_raw + padded, pin + padded + sizeof(SplitInfo)};
+}
+
+static void check_split_args(const vbt_tokenizer* tok, const char* who, const uint8_t* raw, size_t len, bool outputs) {
+    if (!tok || !outputs || (!raw && len)) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+    if (tok->reps.size() > 1) throw Error(VBT_ERR_UNSUPPORTED, std::string(who) + ": a multi-device tokenizer cannot cut lines on the device (sharded input is not implemented)");
+    if ((uint64_t)len >= (1ull << 32)) throw Error(VBT_ERR_INVALID_ARGUMENT, std::string(who) + ": 4 GiB of raw bytes and more (feed it in blocks)");
+}
+
+int vbt_split_lines(const vbt_tokenizer* tok_, const uint8_t* raw, size_t len, int final, uint8_t** text, uint64_t** offsets, uint64_t* n, size_t* consumed) {
+    return guarded([&] {
+        vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
+        check_split_args(tok_, "vbt_split_lines", raw, len, text && offsets && n && consumed);
+        SplitInfo info{};
+        struct Out {  // released on a failure
+            void *text = nullptr, *offs = nullptr;
+            ~Out() { out_free(text); out_free(offs); }
+        } o;
+        TextCall h(tok, *tok->reps[0]);
+        if (len) info = split_on_device(tok, h, raw, len, final != 0, 0).info;
+        o.text = out_alloc(info.text_bytes);
+        o.offs = out_alloc(((size_t)info.n + 1) * 8);
+        if (!o.text || !o.offs) throw std::bad_alloc();
+        static_cast<uint64_t*>(o.offs)[0] = 0;
+        if (info.n) {
+            const size_t text_pad = ((size_t)info.text_bytes + 7) & ~(size_t)7;
+            h.cut = dev_take(tok, h.rep, text_pad + ((size_t)info.n + 1) * 8);
+            uint8_t* d_text = static_cast<uint8_t*>(h.cut->p);
+            uint64_t* d_off = reinterpret_cast<uint64_t*>(d_text + text_pad);
+            hipStream_t stream = h.raw->stream;
+            split_scatter(static_cast<const uint8_t*>(h.raw->p), len, info, static_cast<const uint8_t*>(h.raw->p) + ((len + 15) & ~(size_t)15), d_text, d_off, stream);
+            if (info.text_bytes) HIPX(hipMemcpyAsync(o.text, d_text, info.text_bytes, hipMemcpyDeviceToHost, stream));
+            HIPX(hipMemcpyAsync(o.offs, d_off, ((size_t)info.n + 1) * 8, hipMemcpyDeviceToHost, stream));
+            HIPX(hipStreamSynchronize(stream));
         }
-        if (bytes) HIPX(hipMemcpyAsync(p.d_text, txt, bytes, hipMemcpyHostToDevice, p.stream));
-        HIPX(hipMemcpyAsync(p.d_off, offs, (n + 1) * 8, hipMemcpyHostToDevice, p.stream));
-        p.ws->run(static_cast<const uint8_t*>(p.d_text), p.d_off, n, bytes, p.stream);
-        HIPX(hipMemcpyAsync(tail, p.ws->d_ctrl, 8, hipMemcpyDeviceToHost, p.stream));
-        HIPX(hipMemcpyAsync(total, p.ws->d_line_off + n, 8, hipMemcpyDeviceToHost, p.stream));
-        HIPX(hipStreamSynchronize(p.stream));
-        if (tail[1] & kErrUtf8) {
-            for (uint64_t i = 0; i < n; ++i)
-                if (!valid_utf8(txt + offs[i], offs[i + 1] - offs[i])) throw Error(VBT_ERR_UTF8, "sentence " + std::to_string(i) + " is not valid UTF-8");
-        }
-        if (mecab && tail[1] == (uint32_t)kErrWakatiCap) {  // the capacity alone: the exact need is known now -- grow, render once more
-            if (detail) p.ws->set_detail(true, false, *total); else p.ws->set_mecab(true, false, *total);
-            p.ws->render_text_again(p.stream);
-            HIPX(hipMemcpyAsync(tail, p.ws->d_ctrl, 8, hipMemcpyDeviceToHost, p.stream));
-            HIPX(hipStreamSynchronize(p.stream));
-            if (tail[1] & kErrWakatiCap) throw Error(VBT_ERR_DEVICE, "vbt_tokenize_mecab / vbt_tokenize_detail: the text does not fit a buffer of the size the device asked for");
-        }
-        check_device_errors(tail[1]);
-        const size_t out_bytes = (size_t)*total;
-        if (mecab && bytes) {  // bytes of output per KiB of text, rounded up: the largest seen
-            const uint32_t r = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, ((uint64_t)out_bytes * 1024 + bytes - 1) / bytes + 1);
-            uint32_t cur = per_kib.load(std::memory_order_relaxed);
-            while (r > cur && !per_kib.compare_exchange_weak(cur, r, std::memory_order_relaxed)) {}
-        }
-        h.result = pin_out_alloc(out_bytes);
-        const void* src[2] = {mecab ? p.ws->d_mecab : p.ws->d_wakati, p.ws->d_line_off};
-        void* dst[2] = {h.result, loff};
-        const size_t sz[2] = {out_bytes, line_off ? (size_t)(n + 1) * 8 : 0};
-        if (use_sdma) {
-            std::vector<hsa_signal_t> sigs;
-            bool ok = rep.sdma->issue(src, dst, sz, 2, sigs);
-            ok = Sdma::wait(sigs) && ok;
-            if (!ok) throw Error(VBT_ERR_DEVICE, "device -> host copy of the rendered text failed (hsa_amd_memory_async_copy)");
-        } else {
-            for (int k = 0; k < 2; ++k)
-                if (sz[k]) HIPX(hipMemcpyAsync(dst[k], src[k], sz[k], hipMemcpyDeviceToHost, p.stream));
-            HIPX(hipStreamSynchronize(p.stream));
-        }
-        if (line_off) std::memcpy(line_off, loff, (n + 1) * 8);
-        *out = static_cast<char*>(h.result); *len = out_bytes;
-        h.result = nullptr;
+        *text = static_cast<uint8_t*>(o.text); *offsets = static_cast<uint64_t*>(o.offs);
+        *n = info.n; *consumed = info.consumed;
+        o.text = o.offs = nullptr;
+    });
+}
+
+int vbt_tokenize_stream(const vbt_tokenizer* tok_, int mode, const uint8_t* raw, size_t len, int final, char** out, size_t* out_len, uint64_t* n, size_t* consumed) {
+    return guarded([&] {
+        vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
+        check_split_args(tok_, "vbt_tokenize_stream", raw, len, out && out_len && n && consumed);
+        if (mode != VBT_FORMAT_MECAB && mode != VBT_FORMAT_WAKATI && mode != VBT_FORMAT_DETAIL) throw Error(VBT_ERR_INVALID_ARGUMENT, "vbt_tokenize_stream: no such output mode");
+        *n = 0; *consumed = 0;
+        if (len == 0) return empty_text_result(out, out_len);
+        TextCall h(tok, *tok->reps[0]);
+        const SplitFront f = split_on_device(tok, h, raw, len, final != 0, 16);
+        const SplitInfo& info = f.info;
+        if (info.n == 0) return empty_text_result(out, out_len);  // (no '\n' in a buffer that is not final: nothing consumed)
+        render_text_batch(mode == VBT_FORMAT_DETAIL ? kTextDetail : mode == VBT_FORMAT_MECAB ? kTextMecab : kTextWakati, tok, h, info.n, info.text_bytes,
+            reinterpret_cast<uint32_t*>(f.pinned_behind), nullptr, out, out_len,
+            // (the block's stream has been waited for: the scatter pass may run on the workspace's)
+            [&](PooledWorkspace& p) { split_scatter(f.d_raw, len, info, f.d_scratch, static_cast<uint8_t*>(p.d_text), p.d_off, p.stream); },
+            [&] {  // the lines once more, cut on the host, for the message
+                uint64_t line = 0;
+                for (size_t at = 0; at < info.consumed; ++line) {
+                    const void* nl = std::memchr(raw + at, '\n', info.consumed - at);
+                    const size_t end = nl ? (size_t)(static_cast<const uint8_t*>(nl) - raw) : info.consumed;
+                    const size_t stop = nl && end > at && raw[end - 1] == '\r' ? end - 1 : end;
+                    if (!valid_utf8(raw + at, stop - at)) throw Error(VBT_ERR_UTF8, "line " + std::to_string(line) + " is not valid UTF-8");
+                    at = end + 1;
+                }
+            });
+        *n = info.n; *consumed = info.consumed;
     });
 }
 
@@ -1634,13 +1805,14 @@ int vbt_tokenizer_trim_pool(const vbt_tokenizer* tok_) {
         vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
         if (!tok) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
         std::vector<std::vector<std::unique_ptr<PooledWorkspace>>> ws(tok->reps.size());
+        std::vector<std::vector<std::unique_ptr<DevBlock>>> dev(tok->reps.size());
         std::vector<std::unique_ptr<PinnedBlock>> blocks;
         {
             std::lock_guard<std::mutex> g(tok->pool_mu);
-            for (size_t k = 0; k < tok->reps.size(); ++k) ws[k].swap(tok->reps[k]->pool);
+            for (size_t k = 0; k < tok->reps.size(); ++k) { ws[k].swap(tok->reps[k]->pool); dev[k].swap(tok->reps[k]->dev_pool); }
             blocks.swap(tok->host_pool);
         }
-        for (size_t k = 0; k < ws.size(); ++k) { HIPX(hipSetDevice(tok->reps[k]->t->device())); ws[k].clear(); }
+        for (size_t k = 0; k < ws.size(); ++k) { HIPX(hipSetDevice(tok->reps[k]->t->device())); ws[k].clear(); dev[k].clear(); }
         out_cache_trim();  // the formatter's idle output buffers (process-wide)
     });
 }

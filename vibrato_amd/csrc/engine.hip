@@ -1032,6 +1032,25 @@ void Workspace::reset_connid_counts() {
     acc_lid.clear(); acc_rid.clear();
 }
 
+// ------------------------------------------------------------------ lines cut on the device (split.hip)
+
+uint64_t split_scratch_bytes(uint64_t len) { return 16 + 16 * ((len + VBT_SPLIT_TILE - 1) / VBT_SPLIT_TILE); }  // SplitInfo, a uint4 per tile
+
+void split_count(const uint8_t* d_raw, uint64_t len, bool final, void* d_scratch, void* stream) {
+    if (len == 0 || len > 0xFFFFFFFFull) throw Error(VBT_ERR_INVALID_ARGUMENT, "split_count: 1 .. 4 GiB - 1 bytes");
+    static_assert(sizeof(SplitInfo) == 16, "one 16-byte copy");
+    kern::split_count(reinterpret_cast<hipStream_t>(stream), d_raw, (uint32_t)len, final, reinterpret_cast<uint4*>(d_scratch) + 1, reinterpret_cast<uint32_t*>(d_scratch));
+    HIP_CHECK(hipGetLastError());
+}
+
+void split_scatter(const uint8_t* d_raw, uint64_t len, const SplitInfo& info, const void* d_scratch, uint8_t* d_text, uint64_t* d_offsets, void* stream) {
+    if (info.consumed == 0) return;
+    if (info.consumed > len || info.text_bytes > info.consumed) throw Error(VBT_ERR_INVALID_STATE, "split_scatter: not the counts of this buffer");
+    kern::split_scatter(reinterpret_cast<hipStream_t>(stream), d_raw, (uint32_t)len, info.consumed, reinterpret_cast<const uint4*>(d_scratch) + 1, d_text, d_offsets,
+                        info.n, info.text_bytes, info.tail != 0);
+    HIP_CHECK(hipGetLastError());
+}
+
 // ------------------------------------------------------------------ connection ids by usage
 
 void Tokenizer::finish_calibration(bool done, bool give_up) const {

@@ -173,6 +173,17 @@ struct ConnidReorderInfo {
     uint32_t moved_left = 0, moved_right = 0;  // ids whose device id differs from their dictionary id
 };
 
+// Lines cut on the device (split.hip), for the C ABI's vbt_split_lines / vbt_tokenize_stream.  d_raw: `len` (< 4 GiB)
+// raw bytes in a 16-byte aligned device buffer that is readable up to the next multiple of 16; d_scratch: split_scratch_bytes(len)
+// of device memory, 16-byte aligned.  split_count enqueues the count pass and the scan of the tiles' counts and leaves a SplitInfo
+// in the first 16 bytes of d_scratch; with that back on the host, split_scatter enqueues the pass that writes the sentences' text
+// and offsets[0 .. n] (d_text 4-byte aligned, info.text_bytes long) -- on any stream that runs behind split_count's.  Nothing is
+// launched for len == 0 (split_count: the caller's business) or info.consumed == 0.
+struct SplitInfo { uint32_t n, consumed, text_bytes, tail; };  // tail: the last sentence is the unterminated tail of a final buffer
+uint64_t split_scratch_bytes(uint64_t len);
+void split_count(const uint8_t* d_raw, uint64_t len, bool final, void* d_scratch, void* stream);
+void split_scatter(const uint8_t* d_raw, uint64_t len, const SplitInfo& info, const void* d_scratch, uint8_t* d_text, uint64_t* d_offsets, void* stream);
+
 class Workspace;
 
 class Tokenizer {

@@ -1,4 +1,4 @@
-// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip, wakati.hip, mecab.hip, detail.hip), as plain
+// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip, wakati.hip, mecab.hip, detail.hip, split.hip), as plain
 // functions the host side (engine.hip: Tokenizer, Workspace) calls.  Every launcher enqueues on `stream` and returns.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -84,6 +84,16 @@ void detail_lines(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, 
                   uint64_t* line_off, uint8_t* out, uint64_t out_cap, bool count_tokens);
 void detail_render_again(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, const DevWordParams& w, uint32_t n_tiles, const uint64_t* line_len,
                          const uint64_t* tile_bytes, uint64_t* line_off, uint8_t* out, uint64_t out_cap);
+
+// ---- split.hip: raw bytes cut into sentences (BufRead::lines(): '\n' and "\r\n" end a line) over tiles of VBT_SPLIT_TILE bytes.
+// raw: 16-byte aligned, readable up to the next multiple of 16 behind len.  split_count (count pass + scan of the tiles): tiles[t]
+// (one uint4 per tile of raw) = {'\n's, dropped bytes in front of tile t, ..}, info[0 .. 4) = {n, consumed, bytes of text, 1 when
+// the last sentence is the unterminated tail of a `final` buffer}.  split_scatter, with those four values back from the host: the
+// kept bytes of raw[0 .. consumed) into text (4-byte aligned), offsets[0 .. n] (consumed > 0: the caller launches nothing otherwise).
+uint32_t split_tile();
+void split_count(hipStream_t stream, const uint8_t* raw, uint32_t len, bool final, uint4* tiles, uint32_t* info);
+void split_scatter(hipStream_t stream, const uint8_t* raw, uint32_t len, uint32_t consumed, const uint4* tiles, uint8_t* text, uint64_t* offsets, uint32_t n,
+                   uint32_t text_bytes, bool tail);
 
 // the calibration sample (Tokenizer::maybe_calibrate): up to `want` sentences spread evenly over the batch, copied into s_text / s_offs
 // (s_offs[0 .. k], k = info[0] = the sentences whose text fits cap_bytes; s_src: want words of scratch), on `stream`
