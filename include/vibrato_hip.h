@@ -317,6 +317,43 @@ VBT_API int vbt_split_lines(const vbt_tokenizer* tok, const uint8_t* raw, size_t
 VBT_API int vbt_tokenize_stream(const vbt_tokenizer* tok, int mode, const uint8_t* raw, size_t len, int final, char** out,
                                 size_t* out_len, uint64_t* n, size_t* consumed);
 
+/* ---- N-best (new: MeCab's -N; the reference keeps one best path, lattice.rs:129-151) -------- */
+
+typedef struct vbt_nbest vbt_nbest;
+/* Host text in -> the `nbest` cheapest paths of every sentence out, in host memory (MeCab's -N; no reference counterpart: the sweep
+ * of lattice.rs:129-151 keeps one (min_cost, back pointer) per node, the kernel behind this call keeps `nbest` sorted entries per
+ * node and merges them -- nbest.hip).  The lattice is the one vbt_tokenize_batch takes its path from (same candidates
+ * in the same insertion order, ignore_space, max_grouping_len, user lexicon, unknown words; two homographs of a surface are two
+ * nodes), the cost of a path is the 1-best's i32 arithmetic (word_cost + connection per node + the connection to EOS), and the
+ * paths come in a total order: lower cost first; on equal cost the two paths are compared from EOS backwards and, at the first
+ * node where they differ, the node inserted LATER into its end list comes first -- the `<=` of lattice.rs:141-146 applied
+ * recursively, so path 0 is exactly vbt_tokenize_batch's, record by record.  A sentence yields min(nbest, its paths) paths: an
+ * empty sentence none (worker.rs:50-52), a sentence of skipped spaces one path of no tokens.  total_cost of a record is the cost
+ * accumulated ALONG ITS PATH.  Where an i32 sum wraps the order is that of the wrapped values, entry by entry.
+ * nbest outside 1 .. 16: VBT_ERR_INVALID_ARGUMENT; a multi-device tokenizer: VBT_ERR_UNSUPPORTED; input contract and the other
+ * error codes as vbt_tokenize_batch.  The batch is cut at sentence borders into chunks whose record staging -- nbest x (bytes + 24 x
+ * sentences) records of 24 bytes -- stays within 768 MiB (the workspace rounds capacities up to powers of two and holds as much
+ * again for the packed records, + at most 1 GiB of scratch for the lattices that outgrow LDS); the workspace is kept by the
+ * tokenizer between calls, and calls on one tokenizer take turns.  VBT_NBEST_LDS_KB (read when the tokenizer is created, default
+ * 32, at most 64; 0 = every lattice in global memory) is the LDS a wavefront's lattice may use. */
+VBT_API int vbt_tokenize_nbest(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
+                               uint32_t nbest, vbt_nbest** out);
+VBT_API void vbt_nbest_free(vbt_nbest* r);                                /* releases a result of vbt_tokenize_nbest (MeCab's -N; lattice.rs:129-151) */
+VBT_API uint64_t vbt_nbest_num_sentences(const vbt_nbest* r);             /* sentences of the call (MeCab's -N; lattice.rs:129-151) */
+/* Paths of sentence s, at most the call's nbest (MeCab's -N; lattice.rs:129-151). */
+VBT_API uint32_t vbt_nbest_num_paths(const vbt_nbest* r, uint64_t sentence);
+/* Cost of path `rank` of sentence s: the total_cost of EOS along it (MeCab's -N; lattice.rs:129-151).  Ranks ascend by the order above. */
+VBT_API int vbt_nbest_path_cost(const vbt_nbest* r, uint64_t sentence, uint32_t rank, int32_t* cost);
+/* Its records, in sentence order, and their number (MeCab's -N; lattice.rs:129-151); the pointer lives until vbt_nbest_free. */
+VBT_API int vbt_nbest_path_records(const vbt_nbest* r, uint64_t sentence, uint32_t rank, const vbt_token_rec** records,
+                                   uint32_t* count);
+/* The four raw arrays (MeCab's -N; lattice.rs:129-151): sentence s owns the paths [path_off[s], path_off[s + 1]) (n + 1 entries),
+ * path p the records tokens[tok_off[p] .. tok_off[p + 1]) (paths + 1 entries) and the cost path_cost[p]. */
+VBT_API int vbt_nbest_arrays(const vbt_nbest* r, const uint64_t** path_off, const uint64_t** tok_off,
+                             const int32_t** path_cost, const vbt_token_rec** tokens);
+/* Sentences of the call whose lattice did not fit the LDS tier and was built in global memory (observability; MeCab's -N; lattice.rs:129-151). */
+VBT_API uint64_t vbt_nbest_slab_sentences(const vbt_nbest* r);
+
 /* ---- Device-resident API (zero-copy; what bench.py times) ------------------------ */
 
 /* A workspace owns the device scratch + output buffers for batches of up to

@@ -7,7 +7,7 @@ use std::os::raw::{c_char, c_int, c_void};
 macro_rules! opaque {
     ($($name:ident),*) => { $(#[repr(C)] pub struct $name { _private: [u8; 0] })* };
 }
-opaque!(vbt_dict, vbt_tokenizer, vbt_worker, vbt_batch, vbt_workspace);
+opaque!(vbt_dict, vbt_tokenizer, vbt_worker, vbt_batch, vbt_workspace, vbt_nbest);
 
 pub const VBT_OK: c_int = 0;
 pub const VBT_ERR_INVALID_ARGUMENT: c_int = 1;
@@ -152,6 +152,16 @@ extern "C" {
                               line_off: *mut u64) -> c_int;
     pub fn vbt_tokenize_detail(tok: *const vbt_tokenizer, text: *const u8, offsets: *const u64, n: u64, out: *mut *mut c_char, len: *mut usize,
                                line_off: *mut u64) -> c_int;
+    /// The `nbest` (1 ..= 16) cheapest paths of every sentence (MeCab's `-N`); path 0 is `vbt_tokenize_batch`'s.  `*out` released with `vbt_nbest_free`.
+    pub fn vbt_tokenize_nbest(tok: *const vbt_tokenizer, text: *const u8, offsets: *const u64, n: u64, nbest: u32, out: *mut *mut vbt_nbest) -> c_int;
+    pub fn vbt_nbest_free(r: *mut vbt_nbest);
+    pub fn vbt_nbest_num_sentences(r: *const vbt_nbest) -> u64;
+    pub fn vbt_nbest_num_paths(r: *const vbt_nbest, sentence: u64) -> u32;
+    pub fn vbt_nbest_path_cost(r: *const vbt_nbest, sentence: u64, rank: u32, cost: *mut i32) -> c_int;
+    pub fn vbt_nbest_path_records(r: *const vbt_nbest, sentence: u64, rank: u32, records: *mut *const vbt_token_rec, count: *mut u32) -> c_int;
+    pub fn vbt_nbest_arrays(r: *const vbt_nbest, path_off: *mut *const u64, tok_off: *mut *const u64, path_cost: *mut *const i32,
+                            tokens: *mut *const vbt_token_rec) -> c_int;
+    pub fn vbt_nbest_slab_sentences(r: *const vbt_nbest) -> u64;
     /// Raw bytes -> sentences, the lines cut on the device (`BufRead::lines()` semantics); `*text` / `*offsets` released with `vbt_free`.
     pub fn vbt_split_lines(tok: *const vbt_tokenizer, raw: *const u8, len: usize, is_final: c_int, text: *mut *mut u8, offsets: *mut *mut u64,
                            n: *mut u64, consumed: *mut usize) -> c_int;

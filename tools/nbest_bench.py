@@ -1,0 +1,40 @@
+"""One-call host-to-host rate of Tokenizer.tokenize_nbest on BASELINE config 3's workload (unidic-shaped dictionary, 100 000
+sentences, lognormal lengths) for N in {1, 2, 4, 8, 16} (or argv[3] = "1,4"; argv[1] = sentences, argv[2] = synthetic dictionary), with the same run's tokenize_batch one-call rate beside it.  Prints one
+JSON line; the numbers of DESIGN.md 3.6 / profiles/EXPERIMENTS.md come from here.  Needs an MI355X."""
+import json
+import sys
+import time
+
+import vibrato_amd as V
+from tools import synth
+
+
+def best_of(f, reps):
+    f()  # warm-up: workspaces, pinned blocks, the renumbered device image
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        r = f()
+        ts.append(time.perf_counter() - t)
+    return min(ts), sorted(ts)[len(ts) // 2], r
+
+
+def main():
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 100000
+    sd = synth.SynthDict(sys.argv[2] if len(sys.argv) > 2 else "unidic")
+    dv = V.SystemDictionaryBuilder.from_readers_binmatrix(sd.lex, sd.matrix, sd.num_right, sd.num_left, sd.char_def, sd.unk)
+    text, offs = sd.sentences(n, "lognormal_40", seed=synth.SEED)
+    tok = V.Tokenizer(dv, device=0)
+    tok.calibrate(text=text, offsets=offs)
+    out = {"sentences": n, "bytes": int(len(text))}
+    lo, med, _ = best_of(lambda: tok.tokenize_batch(text=text, offsets=offs), 5)
+    out["tokenize_batch"] = {"best_sentences_per_s": round(n / lo), "median_sentences_per_s": round(n / med)}
+    for k in [int(x) for x in sys.argv[3].split(",")] if len(sys.argv) > 3 else (1, 2, 4, 8, 16):
+        lo, med, r = best_of(lambda: tok.tokenize_nbest(text=text, offsets=offs, n=k), 3)
+        out[f"nbest_{k}"] = {"best_sentences_per_s": round(n / lo), "median_sentences_per_s": round(n / med),
+                             "slab_share": round(r.slab_sentences() / n, 4), "paths": int(r.arrays()[0][-1])}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

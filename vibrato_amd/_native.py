@@ -106,6 +106,14 @@ SIGNATURES = {
     "vbt_tokenize_wakati": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
     "vbt_tokenize_mecab": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
     "vbt_tokenize_detail": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
+    "vbt_tokenize_nbest": (_int, [_vp, _vp, _vp, _u64, _u32, _PP]),
+    "vbt_nbest_free": (None, [_vp]),
+    "vbt_nbest_num_sentences": (_u64, [_vp]),
+    "vbt_nbest_num_paths": (_u32, [_vp, _u64]),
+    "vbt_nbest_path_cost": (_int, [_vp, _u64, _u32, C.POINTER(C.c_int32)]),
+    "vbt_nbest_path_records": (_int, [_vp, _u64, _u32, _PP, C.POINTER(_u32)]),
+    "vbt_nbest_arrays": (_int, [_vp, _PP, _PP, _PP, _PP]),
+    "vbt_nbest_slab_sentences": (_u64, [_vp]),
     "vbt_split_lines": (_int, [_vp, _vp, _sz, _int, _PP, _PP, C.POINTER(_u64), C.POINTER(_sz)]),
     "vbt_tokenize_stream": (_int, [_vp, _int, _vp, _sz, _int, _PP, C.POINTER(_sz), C.POINTER(_u64), C.POINTER(_sz)]),
     "vbt_workspace_new": (_int, [_vp, _u64, _u64, _PP]),

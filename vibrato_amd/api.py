@@ -330,6 +330,25 @@ class Tokenizer:
                                            len(offsets) - 1, C.byref(h)))
         return Batch(self, h)
 
+    def tokenize_nbest(self, sentences=None, n=2, text=None, offsets=None):
+        """The `n` (1..16) cheapest paths of every sentence (MeCab's -N; vbt_tokenize_nbest): the lattice of tokenize_batch, lower
+        cost first, ties towards the node inserted later (compared from EOS backwards), so path 0 is tokenize_batch's.  Returns
+        an NBest.  Single-device tokenizers only."""
+        if sentences is not None:
+            enc = [_b(s) for s in sentences]
+            offsets = np.zeros(len(enc) + 1, dtype=np.uint64)
+            if enc:
+                offsets[1:] = np.cumsum([len(e) for e in enc])
+            text = np.frombuffer(b"".join(enc), dtype=np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if not 0 <= int(n) < 1 << 32:
+            raise VibratoError(1, "vbt_tokenize_nbest: nbest must be 1 .. 16")
+        h = C.c_void_p()
+        N.check(N.lib().vbt_tokenize_nbest(self._handle(), text.ctypes.data if text.size else None, offsets.ctypes.data,
+                                           len(offsets) - 1, int(n), C.byref(h)))
+        return NBest(h)
+
     def tokenize_wakati(self, sentences=None, text=None, offsets=None, with_offsets=False):
         """Host text in -> wakati text out (tokenize/src/main.rs:96-103), rendered on the device (vbt_tokenize_wakati): the bytes of
         tokenize_batch(...).format("wakati") without token records or host formatter threads.  Returns bytes, or with
@@ -597,6 +616,52 @@ class Worker:
         ri, rp = np.zeros(nr, dtype=np.uint32), np.zeros(nr, dtype=np.float64)
         N.check(N.lib().vbt_worker_compute_connid_probs(self._h, li.ctypes.data, lp.ctypes.data, ri.ctypes.data, rp.ctypes.data))
         return list(zip(li.tolist(), lp.tolist())), list(zip(ri.tolist(), rp.tolist()))
+
+
+class NBest:
+    """Results of Tokenizer.tokenize_nbest (host memory): up to n paths per sentence, cheapest first."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                N.lib().vbt_nbest_free(self._h)
+                self._h = None
+        except Exception:  # interpreter teardown: module globals may be gone
+            pass
+
+    def __len__(self):
+        return N.lib().vbt_nbest_num_sentences(self._h)
+
+    def num_paths(self, s):
+        return N.lib().vbt_nbest_num_paths(self._h, s)
+
+    def path(self, s, r):
+        """(cost, records[TOKEN_DTYPE]) of path r of sentence s; the records' total_cost runs along this path."""
+        cost, p, cnt = C.c_int32(), C.c_void_p(), C.c_uint32()
+        N.check(N.lib().vbt_nbest_path_cost(self._h, s, r, C.byref(cost)))
+        N.check(N.lib().vbt_nbest_path_records(self._h, s, r, C.byref(p), C.byref(cnt)))
+        recs = np.frombuffer(C.string_at(p, cnt.value * TOKEN_DTYPE.itemsize), dtype=TOKEN_DTYPE).copy() if cnt.value else np.zeros(0, TOKEN_DTYPE)
+        return cost.value, recs
+
+    def arrays(self):
+        """(path_off[u64, n + 1], tok_off[u64, paths + 1], path_cost[i32, paths], tokens[TOKEN_DTYPE]) copies: sentence s owns the
+        paths path_off[s]:path_off[s + 1], path p the records tok_off[p]:tok_off[p + 1]."""
+        po, to, pc, pt = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        N.check(N.lib().vbt_nbest_arrays(self._h, C.byref(po), C.byref(to), C.byref(pc), C.byref(pt)))
+        path_off = np.frombuffer(C.string_at(po, (len(self) + 1) * 8), dtype=np.uint64).copy()
+        paths = int(path_off[-1])
+        tok_off = np.frombuffer(C.string_at(to, (paths + 1) * 8), dtype=np.uint64).copy()
+        t = int(tok_off[-1])
+        cost = np.frombuffer(C.string_at(pc, paths * 4), dtype=np.int32).copy() if paths else np.zeros(0, np.int32)
+        toks = np.frombuffer(C.string_at(pt, t * TOKEN_DTYPE.itemsize), dtype=TOKEN_DTYPE).copy() if t else np.zeros(0, TOKEN_DTYPE)
+        return path_off, tok_off, cost, toks
+
+    def slab_sentences(self):
+        """Sentences whose lattice left the kernel's LDS tier for global memory (observability)."""
+        return N.lib().vbt_nbest_slab_sentences(self._h)
 
 
 class Batch:

@@ -255,7 +255,18 @@ struct vbt_tokenizer {
     std::atomic<int> calls_in_flight{0};
     std::atomic<uint64_t> call_seq{0}, last_concurrent{0};
     std::atomic<int> out_mode{-1};      // VBT_H2H_OUT: 0 = the packing kernel stores into the pinned block, 1 = SDMA copies (default); published with release once the replicas' Sdma exist
-    ~vbt_tokenizer() { for (auto& r : reps) r->pool.clear(); }  // before the Tokenizers (workspaces reference them)
+    // vbt_tokenize_nbest: one workspace, kept between calls and replaced when a call outgrows it; calls take turns
+    std::mutex nbest_mu;
+    std::unique_ptr<NBestWorkspace> nbest_ws;
+    ~vbt_tokenizer() { nbest_ws.reset(); for (auto& r : reps) r->pool.clear(); }  // before the Tokenizers (workspaces reference them)
+};
+// Results of vbt_tokenize_nbest in host memory: sentence s owns the paths [path_off[s], path_off[s + 1]), path p the records
+// tokens[tok_off[p] .. tok_off[p + 1]) and the cost path_cost[p].
+struct vbt_nbest {
+    uint64_t n = 0, slab_sentences = 0;
+    std::vector<uint64_t> path_off, tok_off;
+    std::vector<int32_t> path_cost;
+    std::vector<vbt_token_rec> tokens;
 };
 struct vbt_workspace { std::unique_ptr<Workspace> w; };
 
@@ -1797,6 +1808,99 @@ int vbt_tokenize_mecab(const vbt_tokenizer* tok, const uint8_t* text, const uint
 
 int vbt_tokenize_detail(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len, uint64_t* line_off) {
     return tokenize_text_on_device(kTextDetail, tok, text, offsets, n, out, len, line_off);
+}
+
+// Staging budget of one N-best run: nbest x (bytes + kSentenceSlack x sentences) token records of 24 bytes.  A batch is cut at
+// sentence borders into chunks that stay within it (a single sentence that does not is a chunk of its own); the packed records,
+// the slab tier's scratch (at most 1 GiB) and the per-path tables come on top: about 2.6 GiB of device memory at most.
+constexpr uint64_t kNBestStageBudget = 768ull << 20;
+
+int vbt_tokenize_nbest(const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, uint32_t nbest, vbt_nbest** out) {
+    return guarded([&] {
+        vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
+        if (!tok || !offsets || !out || (!text && n && offsets[n] != offsets[0])) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (nbest < 1 || nbest > kNBestMax) throw Error(VBT_ERR_INVALID_ARGUMENT, "vbt_tokenize_nbest: nbest must be 1 .. 16");
+        if (tok->reps.size() > 1) throw Error(VBT_ERR_UNSUPPORTED, "vbt_tokenize_nbest: a multi-device tokenizer cannot compute N-best paths (sharding is not implemented)");
+        for (uint64_t i = 1; i <= n; ++i)
+            if (offsets[i] < offsets[i - 1]) throw Error(VBT_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
+        if (offsets[n] - offsets[0] >= 0xFFFFFFFFull || n >= 0xFFFFFFFFull) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch too large (split it)");
+        auto res = std::make_unique<vbt_nbest>();
+        res->n = n;
+        res->path_off.assign(n + 1, 0);
+        res->tok_off.assign(1, 0);
+        std::lock_guard<std::mutex> g(tok->nbest_mu);
+        HIPX(hipSetDevice(tok->t->device()));
+        const uint64_t rec_budget = kNBestStageBudget / sizeof(vbt_token_rec) / nbest;
+        std::vector<uint64_t> offs;
+        std::vector<uint32_t> tmp;
+        for (uint64_t s0 = 0; s0 < n;) {
+            uint64_t s1 = s0 + 1;
+            while (s1 < n && (offsets[s1 + 1] - offsets[s0]) + (uint64_t)kSentenceSlack * (s1 + 1 - s0) <= rec_budget) ++s1;
+            const uint64_t cn = s1 - s0, lo = offsets[s0], bytes = offsets[s1] - lo;
+            if (!tok->nbest_ws || tok->nbest_ws->max_sentences < cn || tok->nbest_ws->max_bytes < bytes || tok->nbest_ws->max_k < nbest) {
+                tok->nbest_ws.reset();
+                tok->nbest_ws = std::make_unique<NBestWorkspace>(*tok->t, round_up_pow2(cn, 64), round_up_pow2(bytes, 4096), nbest);
+            }
+            NBestWorkspace& ws = *tok->nbest_ws;
+            hipStream_t st = reinterpret_cast<hipStream_t>(ws.stream);
+            offs.resize(cn + 1);
+            for (uint64_t i = 0; i <= cn; ++i) offs[i] = offsets[s0 + i] - lo;
+            if (bytes) HIPX(hipMemcpyAsync(ws.d_text, text + lo, bytes, hipMemcpyHostToDevice, st));
+            HIPX(hipMemcpyAsync(ws.d_off, offs.data(), (cn + 1) * 8, hipMemcpyHostToDevice, st));
+            ws.run(cn, bytes, nbest);
+            uint32_t tot[4];
+            ws.totals(tot);
+            if (tot[3] & kErrUtf8)
+                for (uint64_t i = 0; i < cn; ++i)
+                    if (!valid_utf8(text + lo + offs[i], offs[i + 1] - offs[i])) throw Error(VBT_ERR_UTF8, "sentence " + std::to_string(s0 + i) + " is not valid UTF-8");
+            check_device_errors(tot[3]);
+            const uint64_t P = tot[0], T = tot[1], p0 = res->path_cost.size(), t0 = res->tokens.size();
+            res->slab_sentences += tot[2];
+            tmp.resize(std::max<uint64_t>(cn + 1, P + 1));
+            HIPX(hipMemcpyAsync(tmp.data(), ws.nb.path_off, (cn + 1) * 4, hipMemcpyDeviceToHost, st));
+            HIPX(hipStreamSynchronize(st));
+            for (uint64_t i = 0; i <= cn; ++i) res->path_off[s0 + i] = p0 + tmp[i];
+            HIPX(hipMemcpyAsync(tmp.data(), ws.nb.tok_off, (P + 1) * 4, hipMemcpyDeviceToHost, st));
+            HIPX(hipStreamSynchronize(st));
+            res->tok_off.resize(p0 + P + 1);
+            for (uint64_t i = 0; i <= P; ++i) res->tok_off[p0 + i] = t0 + tmp[i];
+            res->path_cost.resize(p0 + P);
+            res->tokens.resize(t0 + T);
+            if (P) HIPX(hipMemcpyAsync(res->path_cost.data() + p0, ws.nb.path_cost_out, P * 4, hipMemcpyDeviceToHost, st));
+            if (T) HIPX(hipMemcpyAsync(res->tokens.data() + t0, ws.nb.tokens, T * sizeof(vbt_token_rec), hipMemcpyDeviceToHost, st));
+            HIPX(hipStreamSynchronize(st));
+            s0 = s1;
+        }
+        *out = res.release();
+    });
+}
+
+void vbt_nbest_free(vbt_nbest* r) { delete r; }
+uint64_t vbt_nbest_num_sentences(const vbt_nbest* r) { return r ? r->n : 0; }
+uint32_t vbt_nbest_num_paths(const vbt_nbest* r, uint64_t s) { return r && s < r->n ? (uint32_t)(r->path_off[s + 1] - r->path_off[s]) : 0; }
+uint64_t vbt_nbest_slab_sentences(const vbt_nbest* r) { return r ? r->slab_sentences : 0; }
+int vbt_nbest_path_cost(const vbt_nbest* r, uint64_t s, uint32_t rank, int32_t* cost) {
+    return guarded([&] {
+        if (!r || !cost || rank >= vbt_nbest_num_paths(r, s)) throw Error(VBT_ERR_INVALID_ARGUMENT, "path index out of range");
+        *cost = r->path_cost[r->path_off[s] + rank];
+    });
+}
+int vbt_nbest_path_records(const vbt_nbest* r, uint64_t s, uint32_t rank, const vbt_token_rec** records, uint32_t* count) {
+    return guarded([&] {
+        if (!r || !records || !count || rank >= vbt_nbest_num_paths(r, s)) throw Error(VBT_ERR_INVALID_ARGUMENT, "path index out of range");
+        const uint64_t p = r->path_off[s] + rank;
+        *count = (uint32_t)(r->tok_off[p + 1] - r->tok_off[p]);
+        *records = r->tokens.data() + r->tok_off[p];
+    });
+}
+int vbt_nbest_arrays(const vbt_nbest* r, const uint64_t** path_off, const uint64_t** tok_off, const int32_t** path_cost, const vbt_token_rec** tokens) {
+    return guarded([&] {
+        if (!r) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (path_off) *path_off = r->path_off.data();
+        if (tok_off) *tok_off = r->tok_off.data();
+        if (path_cost) *path_cost = r->path_cost.data();
+        if (tokens) *tokens = r->tokens.data();
+    });
 }
 
 // Releases every idle pooled workspace and pinned block now (they are re-created on demand).

@@ -80,6 +80,8 @@ Tokenizer::Tokenizer(const Dictionary* dict, bool ignore_space, uint32_t max_gro
     if (device >= count) throw Error(VBT_ERR_INVALID_ARGUMENT, "device: index out of range");
     HIP_CHECK(hipSetDevice(device));
     device_ = device;
+    // N-best LDS tier: 32 KiB per wavefront = five wavefronts on a CU's 160 KiB; at most the 64 KiB a workgroup gets by default
+    nbest_lds_bytes_ = std::min<uint32_t>(env_u32("VBT_NBEST_LDS_KB", 32), 64) * 1024u;
     {
         void* h = nullptr;
         HIP_CHECK(hipHostMalloc(&h, 64, hipHostMallocDefault));
@@ -1030,6 +1032,88 @@ void Workspace::reset_connid_counts() {
     if (has_run) HIP_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(last_stream)));
     zero_now(d_connid, ((size_t)tok.dict().num_left + tok.dict().num_right) * 8);
     acc_lid.clear(); acc_rid.clear();
+}
+
+// ------------------------------------------------------------------ N-best (nbest.hip)
+
+NBestWorkspace::NBestWorkspace(const Tokenizer& t, uint64_t max_s, uint64_t max_b, uint32_t k) : tok(t), max_sentences(max_s), max_bytes(max_b), max_k(k) {
+    try {
+        HIP_CHECK(hipSetDevice(tok.device()));
+        if (max_b >= 0xFFFFFFFFull || max_s >= 0xFFFFFFFFull || k < 1 || k > kNBestMax) throw Error(VBT_ERR_INVALID_ARGUMENT, "N-best workspace: batch too large (split it)");
+        const size_t ns = std::max<uint64_t>(max_s, 1), nbts = std::max<uint64_t>(max_b, 1);
+        const size_t rows = ns * k, slots = (nbts + kSentenceSlack * ns + 1) * k;
+        if (rows >= 0xFFFFFFFFull || slots >= 0xFFFFFFFFull) throw Error(VBT_ERR_INVALID_ARGUMENT, "N-best workspace: batch too large (split it)");
+        auto alloc = [&](size_t bytes) {
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+            allocs_.push_back(p);
+            return p;
+        };
+        hipStream_t s;
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        stream = s;
+        d_text = static_cast<uint8_t*>(alloc(nbts + 16));
+        d_off = static_cast<uint64_t*>(alloc((ns + 1) * 8));
+        nb.stage = static_cast<vbt_token_rec*>(alloc(slots * sizeof(vbt_token_rec)));  // k paths of at most `bytes + slack` tokens per sentence
+        nb.tokens = static_cast<vbt_token_rec*>(alloc(nbts * k * sizeof(vbt_token_rec)));  // tokens <= chars <= bytes, per path
+        nb.path_cnt = static_cast<uint32_t*>(alloc(rows * 4));
+        nb.path_cost = static_cast<int32_t*>(alloc(rows * 4));
+        nb.path_off = static_cast<uint32_t*>(alloc((ns + 1) * 4));
+        nb.tok_off = static_cast<uint32_t*>(alloc((rows + 1) * 4));
+        nb.path_cost_out = static_cast<int32_t*>(alloc(rows * 4));
+        const size_t tiles = rows / 256 + 1;
+        nb.tile_paths = static_cast<uint32_t*>(alloc(tiles * 4));
+        nb.tile_toks = static_cast<uint32_t*>(alloc(tiles * 4));
+        d_npaths = static_cast<uint32_t*>(alloc(ns * 4));
+        d_list = static_cast<uint32_t*>(alloc(ns * 4));
+        d_tile_sums = static_cast<uint32_t*>(alloc((ns / kScanTile + 2) * 4));
+        d_ctrl = static_cast<uint32_t*>(alloc((kCtrlWords + 4) * 4));  // + {entries of the slab tier's list, its work cursor, paths, tokens}
+        nb.totals = d_ctrl + kCtrlWords + 2;
+        // the slab tier's arenas: ~12 k bytes per lattice node; a persistent wave keeps its slab and takes a larger one when a sentence outgrows it
+        scratch_bytes = std::min<uint64_t>(1ull << 30, std::max<uint64_t>(64ull << 20, 4096ull * nbts * k));
+        d_scratch = static_cast<char*>(alloc(scratch_bytes));
+    } catch (...) {
+        release();
+        throw;
+    }
+}
+
+void NBestWorkspace::release() {
+    for (void* p : allocs_) (void)hipFree(p);
+    allocs_.clear();
+    if (stream) (void)hipStreamDestroy(reinterpret_cast<hipStream_t>(stream));
+    stream = nullptr;
+}
+
+NBestWorkspace::~NBestWorkspace() { release(); }
+
+void NBestWorkspace::run(uint64_t n, uint64_t total_bytes, uint32_t k) {
+    if (n > max_sentences || total_bytes > max_bytes || k < 1 || k > max_k) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch exceeds the N-best workspace capacity");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_CHECK(hipSetDevice(tok.device()));
+    HIP_CHECK(hipMemsetAsync(d_ctrl, 0, (kCtrlWords + 4) * 4, st));
+    if (n == 0) return;
+    const DevDict& D = tok.image().dev;  // one image for every launch of the run
+    BatchArgs a{};
+    a.text = d_text; a.offsets = d_off; a.n = (uint32_t)n;
+    a.tok_cnt = d_npaths; a.ctrl = d_ctrl; a.tile_sums = d_tile_sums;
+    a.scratch = d_scratch; a.scratch_bytes = scratch_bytes;
+    NBestArgs b = nb;
+    b.k = k;
+    uint32_t* list_count = d_ctrl + kCtrlWords;
+    const uint64_t work = std::max<uint64_t>(n, total_bytes / 8 + 1);
+    kern::validate_batch((uint32_t)std::min<uint64_t>((work + 255) / 256, 1u << 16), st, a, total_bytes);
+    kern::nbest_lds((uint32_t)n, tok.nbest_lds_bytes(), st, D, a, b, d_list, list_count);
+    kern::nbest_slab((uint32_t)std::min<uint64_t>(n, 1024), st, D, a, b, d_list, list_count, list_count + 1);
+    kern::nbest_pack(st, a, b);
+    HIP_CHECK(hipGetLastError());
+}
+
+void NBestWorkspace::totals(uint32_t out[4]) {
+    uint32_t h[kCtrlWords + 4];
+    HIP_CHECK(hipMemcpyAsync(h, d_ctrl, sizeof(h), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(stream)));
+    HIP_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    out[0] = h[kCtrlWords + 2]; out[1] = h[kCtrlWords + 3]; out[2] = h[kCtrlWords]; out[3] = h[kError];
 }
 
 // ------------------------------------------------------------------ lines cut on the device (split.hip)

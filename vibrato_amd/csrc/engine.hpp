@@ -103,6 +103,22 @@ struct BatchArgs {
     uint32_t gen_level_bytes[3];  // LDS of the levels of gen_long (gen_one files what outgrows it at the smallest level that holds it)
 };
 
+// What an N-best run adds to BatchArgs (nbest.hip).  BatchArgs::tok_cnt[s] = paths of sentence s (<= k).
+struct NBestArgs {
+    uint32_t k;                 // entries per node = paths asked for per sentence, 1 .. kNBestMax
+    vbt_token_rec* stage;       // path r of sentence s: k * sentence_slot(s) + r * (bytes of s + kSentenceSlack), in token order
+    uint32_t* path_cnt;         // [n * k] tokens of path (s, r)
+    int32_t* path_cost;         // [n * k] its cost
+    // packed, sentence-major, rank-minor: sentence s owns the paths [path_off[s], path_off[s + 1]), path p the records [tok_off[p], tok_off[p + 1])
+    uint32_t* path_off;         // [n + 1]
+    uint32_t* tok_off;          // [paths + 1]
+    int32_t* path_cost_out;     // [paths]
+    vbt_token_rec* tokens;
+    uint32_t *tile_paths, *tile_toks;  // per tile of 256 rows (s, r)
+    uint32_t* totals;           // {paths, tokens}
+};
+constexpr uint32_t kNBestMax = 16;
+
 // ctrl[kTotal] total tokens; ctrl[kError] DevError flags; ctrl[kBump..+1] u64 scratch bump pointer;
 // ctrl[kTierCtrl + 2t] = number of sentences tier t passed on, ctrl[kTierCtrl + 2t + 1] = work cursor of tier t
 // ctrl[kNodeCursor] bump pointer of the candidate arrays
@@ -227,6 +243,9 @@ class Tokenizer {
     // detail mode (a tokenizer that renders only MeCab or wakati text pays nothing), freed with the tokenizer; a failed upload leaves
     // nothing allocated and is tried again by the next call.
     const DevWordParams& word_param_table() const;
+    // LDS per wavefront of the N-best kernel's first tier (nbest.hip): VBT_NBEST_LDS_KB, read once when the tokenizer is created;
+    // 0 sends every sentence to the slab tier
+    uint32_t nbest_lds_bytes() const { return nbest_lds_bytes_; }
 
   private:
     void upload_lexicon(const Lexicon& lx, DevLexicon& out);
@@ -264,6 +283,37 @@ class Tokenizer {
     mutable std::once_flag wparam_once_;
     mutable DevWordParams wparam_{};
     mutable void* wparam_alloc_ = nullptr;
+    uint32_t nbest_lds_bytes_ = 0;
+};
+
+// Device buffers and launch sequence of one N-best run (nbest.hip): validate_batch -> the LDS tier (one wavefront per sentence) ->
+// the slab tier (persistent waves, arenas from the scratch bump allocator) -> the pack pass.  Holds batches of up to max_sentences /
+// max_bytes at up to max_k paths per sentence; the staging of the token records is max_k x (max_bytes + kSentenceSlack x
+// max_sentences) records, which is what the caller budgets (vbt_tokenize_nbest cuts its batch into chunks by it).
+class NBestWorkspace {
+  public:
+    NBestWorkspace(const Tokenizer& tok, uint64_t max_sentences, uint64_t max_bytes, uint32_t max_k);
+    ~NBestWorkspace();
+    NBestWorkspace(const NBestWorkspace&) = delete;
+    NBestWorkspace& operator=(const NBestWorkspace&) = delete;
+    // d_text / d_off: the workspace's own input buffers (max_bytes / max_sentences + 1 offsets), filled by the caller on `stream`
+    void run(uint64_t n, uint64_t total_bytes, uint32_t k);  // asynchronous on `stream`
+    // waits for the run; {paths, tokens, sentences the slab tier took, DevError flags}
+    void totals(uint32_t out[4]);
+    const Tokenizer& tok;
+    uint64_t max_sentences, max_bytes;
+    uint32_t max_k;
+    void* stream = nullptr;
+    uint8_t* d_text = nullptr;
+    uint64_t* d_off = nullptr;
+    NBestArgs nb{};
+    uint32_t *d_npaths = nullptr, *d_ctrl = nullptr, *d_list = nullptr, *d_tile_sums = nullptr;
+    char* d_scratch = nullptr;
+    uint64_t scratch_bytes = 0;
+
+  private:
+    std::vector<void*> allocs_;
+    void release();
 };
 
 class Workspace {

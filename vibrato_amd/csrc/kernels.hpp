@@ -43,6 +43,14 @@ void fused_lds(uint32_t workgroups, uint32_t lds_bytes, hipStream_t stream, cons
                uint32_t* cursor, uint32_t* out_list, uint32_t* out_count);
 void fused_global(uint32_t workgroups, hipStream_t stream, const DevDict& D, const BatchArgs& a, const uint32_t* in_list, const uint32_t* in_count, uint32_t* cursor);
 
+// ---- nbest.hip: the K best paths per sentence (one wavefront per sentence, K sorted entries per node) and their pack pass
+// nbest_lds: block b = sentence b, the arena in lds_bytes of LDS (0: everything is filed); out_list / out_count: what did not fit.
+// nbest_slab: persistent waves over that list, arenas from a.scratch (bump pointer ctrl[kBump]).  nbest_pack: tile sums, their
+// scan (nb.totals, path_off[n], tok_off[paths]) and the copy into sentence-major, rank-minor order.
+void nbest_lds(uint32_t n, uint32_t lds_bytes, hipStream_t stream, const DevDict& D, const BatchArgs& a, const NBestArgs& nb, uint32_t* out_list, uint32_t* out_count);
+void nbest_slab(uint32_t workgroups, hipStream_t stream, const DevDict& D, const BatchArgs& a, const NBestArgs& nb, const uint32_t* in_list, const uint32_t* in_count, uint32_t* cursor);
+void nbest_pack(hipStream_t stream, const BatchArgs& a, const NBestArgs& nb);
+
 // ---- pack.hip: token compaction, connector expansion
 uint32_t pack_split();  // workgroups per packing tile
 void tok_tile_scan(hipStream_t stream, const BatchArgs& a, uint32_t* tile_sums, uint32_t n_tiles);
