@@ -354,6 +354,48 @@ VBT_API int vbt_nbest_arrays(const vbt_nbest* r, const uint64_t** path_off, cons
 /* Sentences of the call whose lattice did not fit the LDS tier and was built in global memory (observability; MeCab's -N; lattice.rs:129-151). */
 VBT_API uint64_t vbt_nbest_slab_sentences(const vbt_nbest* r);
 
+/* ---- Lattice marginals (new: MeCab's -m / -l 2 with -t; the reference keeps one best path, lattice.rs:129-151) -------- */
+
+typedef struct vbt_marginal vbt_marginal;
+/* One reported lattice node: its span, its word (word_idx as in vbt_token_rec) and the summed probability of the paths through it. */
+typedef struct vbt_marginal_node {
+    uint32_t start_char, end_char, start_byte, end_byte;
+    uint32_t word_idx;
+    uint32_t reserved; /* 0 */
+    double prob;
+} vbt_marginal_node;
+/* Host text in -> the posterior probability of every lattice node out, in host memory (a forward-backward sweep in float64:
+ * marginal.hip).  The lattice is the one vbt_tokenize_batch takes its path from (same candidates in the same
+ * insertion order, unknown words, user lexicon, ignore_space, max_grouping_len, the same steps with the EOS step and the "input ends
+ * with spaces" rule).  The cost of a path is the EXACT integer sum of its word costs and connection costs, the connection to EOS
+ * included -- it does not wrap as the 1-best's i32 accumulator does.  P(path) = exp(-cost / temperature) / Z, `temperature` in cost
+ * units (MeCab's -t theta with a dictionary cost factor f corresponds to temperature = f / theta); log_z = log of the sum of
+ * exp(-cost / temperature) over all paths; a node's prob = the summed probability of the paths through it.  A node is reported iff
+ * its prob is positive in float64 and >= min_prob -- dead ends (nothing follows them, or nothing reaches them) drop out by that
+ * rule -- and the nodes of a sentence come in lattice order: by start position, then candidate insertion order.  An empty sentence,
+ * and one of spaces only under ignore_space, has no nodes and log_z = 0.
+ * temperature not finite or <= 0, min_prob outside [0, 1] or NaN: VBT_ERR_INVALID_ARGUMENT; a multi-device tokenizer:
+ * VBT_ERR_UNSUPPORTED; input contract and the other error codes as vbt_tokenize_nbest.  The node count of a sentence is not bounded
+ * by its bytes: the node staging starts at 4 records per byte + 64 per sentence (the batch is cut at sentence borders into chunks
+ * that keep this within 768 MiB), sentences that find it full are run again with a staging of the size the run asked for, and a
+ * node list is never truncated.  The workspace is kept by the tokenizer between calls, and calls on one tokenizer take turns.
+ * VBT_MARGINAL_LDS_KB (read when the tokenizer is created, default 32, at most 64; 0 = every lattice in global memory) is the LDS
+ * a wavefront's lattice may use. */
+VBT_API int vbt_tokenize_marginal(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
+                                  double temperature, double min_prob, vbt_marginal** out);
+VBT_API void vbt_marginal_free(vbt_marginal* r);                          /* releases a result of vbt_tokenize_marginal (MeCab's -m; lattice.rs:129-151) */
+VBT_API uint64_t vbt_marginal_num_sentences(const vbt_marginal* r);       /* sentences of the call (MeCab's -m; lattice.rs:129-151) */
+/* log Z of sentence s (MeCab's -m; lattice.rs:129-151). */
+VBT_API int vbt_marginal_log_z(const vbt_marginal* r, uint64_t sentence, double* log_z);
+/* Its reported nodes, in lattice order, and their number (MeCab's -m; lattice.rs:129-151); the pointer lives until vbt_marginal_free. */
+VBT_API int vbt_marginal_nodes(const vbt_marginal* r, uint64_t sentence, const vbt_marginal_node** nodes, uint64_t* count);
+/* The three raw arrays (MeCab's -m; lattice.rs:129-151): sentence s owns the nodes [node_off[s], node_off[s + 1]) (n + 1 entries)
+ * and log_z[s] (n entries). */
+VBT_API int vbt_marginal_arrays(const vbt_marginal* r, const uint64_t** node_off, const double** log_z,
+                                const vbt_marginal_node** nodes);
+/* Sentences of the call whose lattice did not fit the LDS tier and was built in global memory (observability; MeCab's -m; lattice.rs:129-151). */
+VBT_API uint64_t vbt_marginal_slab_sentences(const vbt_marginal* r);
+
 /* ---- Device-resident API (zero-copy; what bench.py times) ------------------------ */
 
 /* A workspace owns the device scratch + output buffers for batches of up to

@@ -7,7 +7,7 @@ use std::os::raw::{c_char, c_int, c_void};
 macro_rules! opaque {
     ($($name:ident),*) => { $(#[repr(C)] pub struct $name { _private: [u8; 0] })* };
 }
-opaque!(vbt_dict, vbt_tokenizer, vbt_worker, vbt_batch, vbt_workspace, vbt_nbest);
+opaque!(vbt_dict, vbt_tokenizer, vbt_worker, vbt_batch, vbt_workspace, vbt_nbest, vbt_marginal);
 
 pub const VBT_OK: c_int = 0;
 pub const VBT_ERR_INVALID_ARGUMENT: c_int = 1;
@@ -37,6 +37,21 @@ pub struct vbt_token_rec {
     /// `lex_type << 30 | word_id`
     pub word_idx: u32,
     pub total_cost: i32,
+}
+
+/// 32-byte record of one reported lattice node of `vbt_tokenize_marginal`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct vbt_marginal_node {
+    pub start_char: u32,
+    pub end_char: u32,
+    pub start_byte: u32,
+    pub end_byte: u32,
+    /// `lex_type << 30 | word_id`
+    pub word_idx: u32,
+    pub reserved: u32,
+    /// summed probability of the paths through the node
+    pub prob: f64,
 }
 
 #[repr(C)]
@@ -168,6 +183,17 @@ extern "C" {
     /// Raw bytes -> rendered text (`mode`: `VBT_FORMAT_*`), the lines cut on the device; `*out` released with `vbt_free`.
     pub fn vbt_tokenize_stream(tok: *const vbt_tokenizer, mode: c_int, raw: *const u8, len: usize, is_final: c_int, out: *mut *mut c_char,
                                out_len: *mut usize, n: *mut u64, consumed: *mut usize) -> c_int;
+
+    // ---- Lattice marginals
+    /// The posterior probability of every lattice node under P(path) ~ exp(-cost / temperature) (MeCab's `-m` with `-t`).  `*out` released with `vbt_marginal_free`.
+    pub fn vbt_tokenize_marginal(tok: *const vbt_tokenizer, text: *const u8, offsets: *const u64, n: u64, temperature: f64, min_prob: f64,
+                                 out: *mut *mut vbt_marginal) -> c_int;
+    pub fn vbt_marginal_free(r: *mut vbt_marginal);
+    pub fn vbt_marginal_num_sentences(r: *const vbt_marginal) -> u64;
+    pub fn vbt_marginal_log_z(r: *const vbt_marginal, sentence: u64, log_z: *mut f64) -> c_int;
+    pub fn vbt_marginal_nodes(r: *const vbt_marginal, sentence: u64, nodes: *mut *const vbt_marginal_node, count: *mut u64) -> c_int;
+    pub fn vbt_marginal_arrays(r: *const vbt_marginal, node_off: *mut *const u64, log_z: *mut *const f64, nodes: *mut *const vbt_marginal_node) -> c_int;
+    pub fn vbt_marginal_slab_sentences(r: *const vbt_marginal) -> u64;
 
     // ---- Device-resident API
     pub fn vbt_workspace_new(tok: *const vbt_tokenizer, max_sentences: u64, max_bytes: u64, out: *mut *mut vbt_workspace) -> c_int;

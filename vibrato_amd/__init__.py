@@ -2,9 +2,9 @@
 tokenize() path of daac-tools/vibrato.  The compute lives in csrc/ (HIP kernels + C ABI,
 built into lib/libvibrato_hip.so); this package is the thin host mirror of vibrato's
 Dictionary / Tokenizer / Worker / Token API."""
-from .api import (Batch, Dictionary, NBest, SystemDictionaryBuilder, Token, Tokenizer, VibratoError, Worker,  # noqa: F401
-                  Workspace, TOKEN_DTYPE, LEX_NAMES, compute_connid_probs)
+from .api import (Batch, Dictionary, Marginal, NBest, SystemDictionaryBuilder, Token, Tokenizer, VibratoError, Worker,  # noqa: F401
+                  Workspace, MARGINAL_NODE_DTYPE, TOKEN_DTYPE, LEX_NAMES, compute_connid_probs)
 from ._native import DETAIL_ROUND, MECAB_ROUND, SPLIT_TILE, WAKATI_ROUND  # noqa: F401
 
-__all__ = ["DETAIL_ROUND", "MECAB_ROUND", "SPLIT_TILE", "WAKATI_ROUND", "Batch", "Dictionary", "NBest", "SystemDictionaryBuilder", "Token", "Tokenizer", "VibratoError", "Worker",
-           "Workspace", "TOKEN_DTYPE", "LEX_NAMES", "compute_connid_probs"]
+__all__ = ["DETAIL_ROUND", "MECAB_ROUND", "SPLIT_TILE", "WAKATI_ROUND", "Batch", "Dictionary", "Marginal", "NBest", "SystemDictionaryBuilder", "Token", "Tokenizer", "VibratoError", "Worker",
+           "Workspace", "MARGINAL_NODE_DTYPE", "TOKEN_DTYPE", "LEX_NAMES", "compute_connid_probs"]

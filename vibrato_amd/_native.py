@@ -114,6 +114,13 @@ SIGNATURES = {
     "vbt_nbest_path_records": (_int, [_vp, _u64, _u32, _PP, C.POINTER(_u32)]),
     "vbt_nbest_arrays": (_int, [_vp, _PP, _PP, _PP, _PP]),
     "vbt_nbest_slab_sentences": (_u64, [_vp]),
+    "vbt_tokenize_marginal": (_int, [_vp, _vp, _vp, _u64, C.c_double, C.c_double, _PP]),
+    "vbt_marginal_free": (None, [_vp]),
+    "vbt_marginal_num_sentences": (_u64, [_vp]),
+    "vbt_marginal_log_z": (_int, [_vp, _u64, C.POINTER(C.c_double)]),
+    "vbt_marginal_nodes": (_int, [_vp, _u64, _PP, C.POINTER(_u64)]),
+    "vbt_marginal_arrays": (_int, [_vp, _PP, _PP, _PP]),
+    "vbt_marginal_slab_sentences": (_u64, [_vp]),
     "vbt_split_lines": (_int, [_vp, _vp, _sz, _int, _PP, _PP, C.POINTER(_u64), C.POINTER(_sz)]),
     "vbt_tokenize_stream": (_int, [_vp, _int, _vp, _sz, _int, _PP, C.POINTER(_sz), C.POINTER(_u64), C.POINTER(_sz)]),
     "vbt_workspace_new": (_int, [_vp, _u64, _u64, _PP]),

@@ -14,6 +14,8 @@ from ._native import VibratoError  # noqa: F401
 LEX_NAMES = ("System", "User", "Unknown")  # LexType, dictionary.rs:30-40
 TOKEN_DTYPE = np.dtype([("start_char", "<u4"), ("end_char", "<u4"), ("start_byte", "<u4"),
                         ("end_byte", "<u4"), ("word_idx", "<u4"), ("total_cost", "<i4")])
+MARGINAL_NODE_DTYPE = np.dtype([("start_char", "<u4"), ("end_char", "<u4"), ("start_byte", "<u4"), ("end_byte", "<u4"),
+                                ("word_idx", "<u4"), ("reserved", "<u4"), ("prob", "<f8")])  # vbt_marginal_node
 
 
 def _b(x):
@@ -349,6 +351,25 @@ class Tokenizer:
                                            len(offsets) - 1, int(n), C.byref(h)))
         return NBest(h)
 
+    def tokenize_marginal(self, sentences=None, temperature=None, min_prob=0.0, text=None, offsets=None):
+        """The posterior probability of every lattice node under P(path) ~ exp(-cost / temperature) (MeCab's -m with -t;
+        vbt_tokenize_marginal): the lattice of tokenize_batch, exact integer path costs, float64 sums.  Nodes whose probability is
+        positive and >= min_prob are reported, in lattice order.  Returns a Marginal.  Single-device tokenizers only."""
+        if sentences is not None:
+            enc = [_b(s) for s in sentences]
+            offsets = np.zeros(len(enc) + 1, dtype=np.uint64)
+            if enc:
+                offsets[1:] = np.cumsum([len(e) for e in enc])
+            text = np.frombuffer(b"".join(enc), dtype=np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if temperature is None:
+            raise VibratoError(1, "vbt_tokenize_marginal: temperature must be finite and > 0")
+        h = C.c_void_p()
+        N.check(N.lib().vbt_tokenize_marginal(self._handle(), text.ctypes.data if text.size else None, offsets.ctypes.data,
+                                              len(offsets) - 1, float(temperature), float(min_prob), C.byref(h)))
+        return Marginal(h)
+
     def tokenize_wakati(self, sentences=None, text=None, offsets=None, with_offsets=False):
         """Host text in -> wakati text out (tokenize/src/main.rs:96-103), rendered on the device (vbt_tokenize_wakati): the bytes of
         tokenize_batch(...).format("wakati") without token records or host formatter threads.  Returns bytes, or with
@@ -662,6 +683,52 @@ class NBest:
     def slab_sentences(self):
         """Sentences whose lattice left the kernel's LDS tier for global memory (observability)."""
         return N.lib().vbt_nbest_slab_sentences(self._h)
+
+
+class Marginal:
+    """Results of Tokenizer.tokenize_marginal (host memory): log Z and the reported lattice nodes of every sentence."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                N.lib().vbt_marginal_free(self._h)
+                self._h = None
+        except Exception:  # interpreter teardown: module globals may be gone
+            pass
+
+    def __len__(self):
+        return N.lib().vbt_marginal_num_sentences(self._h)
+
+    def log_z(self, s):
+        z = C.c_double()
+        N.check(N.lib().vbt_marginal_log_z(self._h, s, C.byref(z)))
+        return z.value
+
+    def nodes(self, s):
+        """The reported nodes of sentence s in lattice order (by start position, then insertion order): MARGINAL_NODE_DTYPE."""
+        p, cnt = C.c_void_p(), C.c_uint64()
+        N.check(N.lib().vbt_marginal_nodes(self._h, s, C.byref(p), C.byref(cnt)))
+        if not cnt.value:
+            return np.zeros(0, MARGINAL_NODE_DTYPE)
+        return np.frombuffer(C.string_at(p, cnt.value * MARGINAL_NODE_DTYPE.itemsize), dtype=MARGINAL_NODE_DTYPE).copy()
+
+    def arrays(self):
+        """(node_off[u64, n + 1], log_z[f8, n], nodes[MARGINAL_NODE_DTYPE]) copies: sentence s owns the nodes node_off[s]:node_off[s + 1]."""
+        no, lz, nd = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        N.check(N.lib().vbt_marginal_arrays(self._h, C.byref(no), C.byref(lz), C.byref(nd)))
+        n = len(self)
+        node_off = np.frombuffer(C.string_at(no, (n + 1) * 8), dtype=np.uint64).copy()
+        log_z = np.frombuffer(C.string_at(lz, n * 8), dtype=np.float64).copy() if n else np.zeros(0, np.float64)
+        t = int(node_off[-1])
+        nodes = np.frombuffer(C.string_at(nd, t * MARGINAL_NODE_DTYPE.itemsize), dtype=MARGINAL_NODE_DTYPE).copy() if t else np.zeros(0, MARGINAL_NODE_DTYPE)
+        return node_off, log_z, nodes
+
+    def slab_sentences(self):
+        """Sentences whose lattice left the kernel's LDS tier for global memory (observability)."""
+        return N.lib().vbt_marginal_slab_sentences(self._h)
 
 
 class Batch:

@@ -7,6 +7,8 @@
 --compile-to PATH writes the loaded dictionary back out as system.dic.zst (compile/src/main.rs:98).  Lines are read with the semantics of BufRead::lines()
 (`\\n` / `\\r\\n` stripped) and tokenized in blocks of --block lines per GPU batch; the bytes
 written are exactly those of the reference CLI for the same mode.
+`-O marginal --temperature T [--min-prob P]` (no counterpart in the reference; MeCab's -m with -t) prints every lattice node
+whose posterior probability is at least P as `surface\\tfeature\\tprob`, then `EOS`.
 """
 import argparse
 import os
@@ -23,12 +25,29 @@ def read_sources(d):
     return out
 
 
+def render_marginal(d, lines, mg):
+    """-O marginal: "surface\\tfeature\\tprob" per reported lattice node (lattice order), "EOS" per sentence -- formatted here from
+    the arrays of Tokenizer.tokenize_marginal."""
+    node_off, _, nodes = mg.arrays()
+    feature, out = {}, []
+    for s, line in enumerate(lines):
+        for g in nodes[int(node_off[s]):int(node_off[s + 1])]:
+            w = int(g["word_idx"])
+            if w not in feature:
+                feature[w] = d.word_feature(w >> 30, w & 0x3FFFFFFF).encode("utf-8")
+            out += [line[int(g["start_byte"]):int(g["end_byte"])], b"\t", feature[w], b"\t%.6f\n" % float(g["prob"])]
+        out.append(b"EOS\n")
+    return b"".join(out)
+
+
 def main(argv=None, stdin=None, stdout=None):
     ap = argparse.ArgumentParser(prog="tokenize", description="Predicts morphemes")
     ap.add_argument("-i", "--sysdic", required=True, help="System dictionary (in zstd), or a directory with lex.csv, matrix.def, char.def, unk.def")
     ap.add_argument("--compile-to", default=None, help="also write the dictionary as system.dic.zst (zstd level 19) to this path")
     ap.add_argument("-u", "--userlex-csv", default=None, help="User lexicon file.")
-    ap.add_argument("-O", "--output-mode", default="mecab", choices=["mecab", "wakati", "detail"])
+    ap.add_argument("-O", "--output-mode", default="mecab", choices=["mecab", "wakati", "detail", "marginal"])
+    ap.add_argument("--temperature", type=float, default=None, help="marginal mode: P(path) ~ exp(-cost / temperature), in cost units (required there)")
+    ap.add_argument("--min-prob", type=float, default=0.0, help="marginal mode: report the lattice nodes whose probability is at least this")
     ap.add_argument("-S", "--ignore-space", action="store_true", help="Ignores white spaces in input strings.")
     ap.add_argument("-M", "--max-grouping-len", type=int, default=None, help="Maximum length of unknown words.")
     ap.add_argument("--block", type=int, default=65536, help="lines per GPU batch")
@@ -58,8 +77,13 @@ def main(argv=None, stdin=None, stdout=None):
     # tokenize_mecab / tokenize_detail -- and the output stage only writes it; DESIGN.md 3.4a-c hold the measurements behind that)
     import queue
     import threading
-    text_on_device = tok.num_devices() == 1
-    tokenize_text = {"wakati": tok.tokenize_wakati, "mecab": tok.tokenize_mecab, "detail": tok.tokenize_detail}[args.output_mode]
+    text_on_device = tok.num_devices() == 1 or args.output_mode == "marginal"
+    if args.output_mode == "marginal":
+        if args.temperature is None:
+            ap.error("-O marginal needs --temperature")
+        tokenize_text = lambda lines: render_marginal(d, lines, tok.tokenize_marginal(lines, args.temperature, args.min_prob))  # noqa: E731
+    else:
+        tokenize_text = {"wakati": tok.tokenize_wakati, "mecab": tok.tokenize_mecab, "detail": tok.tokenize_detail}[args.output_mode]
     blocks, batches = queue.Queue(maxsize=2), queue.Queue(maxsize=2)
     failure = []
 

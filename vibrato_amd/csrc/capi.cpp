@@ -258,7 +258,17 @@ struct vbt_tokenizer {
     // vbt_tokenize_nbest: one workspace, kept between calls and replaced when a call outgrows it; calls take turns
     std::mutex nbest_mu;
     std::unique_ptr<NBestWorkspace> nbest_ws;
-    ~vbt_tokenizer() { nbest_ws.reset(); for (auto& r : reps) r->pool.clear(); }  // before the Tokenizers (workspaces reference them)
+    // vbt_tokenize_marginal: likewise
+    std::mutex marginal_mu;
+    std::unique_ptr<MarginalWorkspace> marginal_ws;
+    ~vbt_tokenizer() { nbest_ws.reset(); marginal_ws.reset(); for (auto& r : reps) r->pool.clear(); }  // before the Tokenizers (workspaces reference them)
+};
+// Results of vbt_tokenize_marginal in host memory: sentence s owns the nodes [node_off[s], node_off[s + 1]) and log_z[s].
+struct vbt_marginal {
+    uint64_t n = 0, slab_sentences = 0;
+    std::vector<uint64_t> node_off;
+    std::vector<double> log_z;
+    std::vector<vbt_marginal_node> nodes;
 };
 // Results of vbt_tokenize_nbest in host memory: sentence s owns the paths [path_off[s], path_off[s + 1]), path p the records
 // tokens[tok_off[p] .. tok_off[p + 1]) and the cost path_cost[p].
@@ -1900,6 +1910,91 @@ int vbt_nbest_arrays(const vbt_nbest* r, const uint64_t** path_off, const uint64
         if (tok_off) *tok_off = r->tok_off.data();
         if (path_cost) *path_cost = r->path_cost.data();
         if (tokens) *tokens = r->tokens.data();
+    });
+}
+
+// Staging budget of one marginal run: kMarginalNodesPerByte x bytes + kMarginalNodesPerSentence x sentences node records of 32
+// bytes to start with (a run that asks for more gets more: MarginalWorkspace::run).  A batch is cut at sentence borders into chunks
+// that stay within it (a single sentence that does not is a chunk of its own); the packed records are as much again.
+constexpr uint64_t kMarginalStageBudget = 768ull << 20;
+
+int vbt_tokenize_marginal(const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, double temperature, double min_prob,
+                          vbt_marginal** out) {
+    return guarded([&] {
+        vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
+        if (!tok || !offsets || !out || (!text && n && offsets[n] != offsets[0])) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (!std::isfinite(temperature) || !(temperature > 0.0)) throw Error(VBT_ERR_INVALID_ARGUMENT, "vbt_tokenize_marginal: temperature must be finite and > 0");
+        if (!(min_prob >= 0.0 && min_prob <= 1.0)) throw Error(VBT_ERR_INVALID_ARGUMENT, "vbt_tokenize_marginal: min_prob must be within [0, 1]");
+        if (tok->reps.size() > 1) throw Error(VBT_ERR_UNSUPPORTED, "vbt_tokenize_marginal: a multi-device tokenizer cannot compute marginals (sharding is not implemented)");
+        for (uint64_t i = 1; i <= n; ++i)
+            if (offsets[i] < offsets[i - 1]) throw Error(VBT_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
+        if (offsets[n] - offsets[0] >= 0xFFFFFFFFull || n >= 0xFFFFFFFFull) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch too large (split it)");
+        auto res = std::make_unique<vbt_marginal>();
+        res->n = n;
+        res->node_off.assign(n + 1, 0);
+        res->log_z.assign(n, 0.0);
+        std::lock_guard<std::mutex> g(tok->marginal_mu);
+        HIPX(hipSetDevice(tok->t->device()));
+        const uint64_t rec_budget = kMarginalStageBudget / sizeof(vbt_marginal_node);
+        std::vector<uint64_t> offs;
+        std::vector<uint32_t> tmp;
+        for (uint64_t s0 = 0; s0 < n;) {
+            uint64_t s1 = s0 + 1;
+            while (s1 < n && kMarginalNodesPerByte * (offsets[s1 + 1] - offsets[s0]) + kMarginalNodesPerSentence * (s1 + 1 - s0) <= rec_budget) ++s1;
+            const uint64_t cn = s1 - s0, lo = offsets[s0], bytes = offsets[s1] - lo;
+            if (!tok->marginal_ws || tok->marginal_ws->max_sentences < cn || tok->marginal_ws->max_bytes < bytes) {
+                tok->marginal_ws.reset();
+                tok->marginal_ws = std::make_unique<MarginalWorkspace>(*tok->t, round_up_pow2(cn, 64), round_up_pow2(bytes, 4096));
+            }
+            MarginalWorkspace& ws = *tok->marginal_ws;
+            hipStream_t st = reinterpret_cast<hipStream_t>(ws.stream);
+            offs.resize(cn + 1);
+            for (uint64_t i = 0; i <= cn; ++i) offs[i] = offsets[s0 + i] - lo;
+            if (bytes) HIPX(hipMemcpyAsync(ws.d_text, text + lo, bytes, hipMemcpyHostToDevice, st));
+            HIPX(hipMemcpyAsync(ws.d_off, offs.data(), (cn + 1) * 8, hipMemcpyHostToDevice, st));
+            uint64_t tot[3];
+            ws.run(cn, bytes, temperature, min_prob, tot);
+            if (tot[2] & kErrUtf8)
+                for (uint64_t i = 0; i < cn; ++i)
+                    if (!valid_utf8(text + lo + offs[i], offs[i + 1] - offs[i])) throw Error(VBT_ERR_UTF8, "sentence " + std::to_string(s0 + i) + " is not valid UTF-8");
+            check_device_errors((uint32_t)tot[2]);
+            const uint64_t T = tot[0], t0 = res->nodes.size();
+            res->slab_sentences += tot[1];
+            tmp.resize(cn + 1);
+            HIPX(hipMemcpyAsync(tmp.data(), ws.mg.node_off, (cn + 1) * 4, hipMemcpyDeviceToHost, st));
+            HIPX(hipMemcpyAsync(res->log_z.data() + s0, ws.mg.log_z, cn * 8, hipMemcpyDeviceToHost, st));
+            res->nodes.resize(t0 + T);
+            if (T) HIPX(hipMemcpyAsync(res->nodes.data() + t0, ws.mg.nodes, T * sizeof(vbt_marginal_node), hipMemcpyDeviceToHost, st));
+            HIPX(hipStreamSynchronize(st));
+            for (uint64_t i = 0; i <= cn; ++i) res->node_off[s0 + i] = t0 + tmp[i];
+            s0 = s1;
+        }
+        *out = res.release();
+    });
+}
+
+void vbt_marginal_free(vbt_marginal* r) { delete r; }
+uint64_t vbt_marginal_num_sentences(const vbt_marginal* r) { return r ? r->n : 0; }
+uint64_t vbt_marginal_slab_sentences(const vbt_marginal* r) { return r ? r->slab_sentences : 0; }
+int vbt_marginal_log_z(const vbt_marginal* r, uint64_t s, double* log_z) {
+    return guarded([&] {
+        if (!r || !log_z || s >= r->n) throw Error(VBT_ERR_INVALID_ARGUMENT, "sentence index out of range");
+        *log_z = r->log_z[s];
+    });
+}
+int vbt_marginal_nodes(const vbt_marginal* r, uint64_t s, const vbt_marginal_node** nodes, uint64_t* count) {
+    return guarded([&] {
+        if (!r || !nodes || !count || s >= r->n) throw Error(VBT_ERR_INVALID_ARGUMENT, "sentence index out of range");
+        *count = r->node_off[s + 1] - r->node_off[s];
+        *nodes = r->nodes.data() + r->node_off[s];
+    });
+}
+int vbt_marginal_arrays(const vbt_marginal* r, const uint64_t** node_off, const double** log_z, const vbt_marginal_node** nodes) {
+    return guarded([&] {
+        if (!r) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (node_off) *node_off = r->node_off.data();
+        if (log_z) *log_z = r->log_z.data();
+        if (nodes) *nodes = r->nodes.data();
     });
 }
 

@@ -82,6 +82,8 @@ Tokenizer::Tokenizer(const Dictionary* dict, bool ignore_space, uint32_t max_gro
     device_ = device;
     // N-best LDS tier: 32 KiB per wavefront = five wavefronts on a CU's 160 KiB; at most the 64 KiB a workgroup gets by default
     nbest_lds_bytes_ = std::min<uint32_t>(env_u32("VBT_NBEST_LDS_KB", 32), 64) * 1024u;
+    marginal_lds_bytes_ = std::min<uint32_t>(env_u32("VBT_MARGINAL_LDS_KB", 32), 64) * 1024u;
+    marginal_stage_bytes_ = std::min<uint32_t>(env_u32("VBT_MARGINAL_STAGE_KB", 0), 1u << 20) * 1024u;
     {
         void* h = nullptr;
         HIP_CHECK(hipHostMalloc(&h, 64, hipHostMallocDefault));
@@ -1114,6 +1116,147 @@ void NBestWorkspace::totals(uint32_t out[4]) {
     HIP_CHECK(hipMemcpyAsync(h, d_ctrl, sizeof(h), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(stream)));
     HIP_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
     out[0] = h[kCtrlWords + 2]; out[1] = h[kCtrlWords + 3]; out[2] = h[kCtrlWords]; out[3] = h[kError];
+}
+
+// ------------------------------------------------------------------ lattice marginals (marginal.hip)
+
+namespace {
+// words behind the control block: {entries of the slab tier's list, its work cursor, node-staging cursor (u64), sentences that found
+// the staging full, work cursor of their second run, nodes after the pack pass, -}
+enum { kMgList = 0, kMgListCursor = 1, kMgStageCursor = 2, kMgOflow = 4, kMgOflowCursor = 5, kMgTotal = 6, kMgWords = 8 };
+}  // namespace
+
+MarginalWorkspace::MarginalWorkspace(const Tokenizer& t, uint64_t max_s, uint64_t max_b) : tok(t), max_sentences(max_s), max_bytes(max_b) {
+    try {
+        HIP_CHECK(hipSetDevice(tok.device()));
+        if (max_b >= 0xFFFFFFFFull || max_s >= 0xFFFFFFFFull) throw Error(VBT_ERR_INVALID_ARGUMENT, "marginal workspace: batch too large (split it)");
+        const size_t ns = std::max<uint64_t>(max_s, 1), nbts = std::max<uint64_t>(max_b, 1);
+        auto alloc = [&](size_t bytes) {
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+            allocs_.push_back(p);
+            return p;
+        };
+        hipStream_t s;
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        stream = s;
+        d_text = static_cast<uint8_t*>(alloc(nbts + 16));
+        d_off = static_cast<uint64_t*>(alloc((ns + 1) * 8));
+        mg.node_base = static_cast<uint64_t*>(alloc(ns * 8));
+        mg.log_z = static_cast<double*>(alloc(ns * 8));
+        mg.oflow_list = static_cast<uint32_t*>(alloc(ns * 4));
+        mg.node_off = static_cast<uint32_t*>(alloc((ns + 1) * 4));
+        mg.tile_nodes = static_cast<uint32_t*>(alloc((ns / 256 + 1) * 4));
+        d_cnt = static_cast<uint32_t*>(alloc(ns * 4));
+        d_list = static_cast<uint32_t*>(alloc(ns * 4));
+        d_tile_sums = static_cast<uint32_t*>(alloc((ns / kScanTile + 2) * 4));
+        d_ctrl = static_cast<uint32_t*>(alloc((kCtrlWords + kMgWords) * 4));
+        mg.stage_cursor = reinterpret_cast<unsigned long long*>(d_ctrl + kCtrlWords + kMgStageCursor);
+        mg.oflow_count = d_ctrl + kCtrlWords + kMgOflow;
+        mg.totals = d_ctrl + kCtrlWords + kMgTotal;
+        // the slab tier's arenas: ~30 bytes per lattice node + the connection-cost staging; a persistent wave keeps its slab and takes a larger one when a sentence outgrows it
+        scratch_bytes = std::min<uint64_t>(1ull << 30, std::max<uint64_t>(64ull << 20, 2048ull * nbts));
+        d_scratch = static_cast<char*>(alloc(scratch_bytes));
+        grow_stage(kMarginalNodesPerByte * nbts + kMarginalNodesPerSentence * ns);
+    } catch (...) {
+        release();
+        throw;
+    }
+}
+
+// a staging (and a packed buffer) of at least `records` records; what the staging holds stays
+void MarginalWorkspace::grow_stage(uint64_t records) {
+    if (records <= mg.stage_cap) return;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    void *ns = nullptr, *nn = nullptr;
+    HIP_CHECK(hipMalloc(&ns, records * sizeof(vbt_marginal_node)));
+    if (hipMalloc(&nn, records * sizeof(vbt_marginal_node)) != hipSuccess) {
+        (void)hipFree(ns);
+        throw Error(VBT_ERR_DEVICE, "marginal workspace: no device memory for the node records");
+    }
+    if (mg.stage_cap) {
+        const hipError_t e1 = hipMemcpyAsync(ns, mg.stage, mg.stage_cap * sizeof(vbt_marginal_node), hipMemcpyDeviceToDevice, st);
+        const hipError_t e2 = hipStreamSynchronize(st);
+        if (e1 != hipSuccess || e2 != hipSuccess) {
+            (void)hipFree(ns); (void)hipFree(nn);
+            throw Error(VBT_ERR_DEVICE, "marginal workspace: copying the node staging failed");
+        }
+    }
+    (void)hipFree(mg.stage); (void)hipFree(mg.nodes);
+    mg.stage = static_cast<vbt_marginal_node*>(ns);
+    mg.nodes = static_cast<vbt_marginal_node*>(nn);
+    mg.stage_cap = records;
+}
+
+void MarginalWorkspace::release() {
+    for (void* p : allocs_) (void)hipFree(p);
+    allocs_.clear();
+    (void)hipFree(mg.stage); (void)hipFree(mg.nodes);
+    mg.stage = mg.nodes = nullptr;
+    mg.stage_cap = 0;
+    if (stream) (void)hipStreamDestroy(reinterpret_cast<hipStream_t>(stream));
+    stream = nullptr;
+}
+
+MarginalWorkspace::~MarginalWorkspace() { release(); }
+
+void MarginalWorkspace::launch(uint64_t n, uint64_t total_bytes, const MarginalArgs& m, uint32_t again) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const DevDict& D = tok.image().dev;  // one image for every launch of the run
+    BatchArgs a{};
+    a.text = d_text; a.offsets = d_off; a.n = (uint32_t)n;
+    a.tok_cnt = d_cnt; a.ctrl = d_ctrl; a.tile_sums = d_tile_sums;
+    a.scratch = d_scratch; a.scratch_bytes = scratch_bytes;
+    MarginalArgs b = m;
+    b.stage_cells = tok.marginal_stage_bytes() / (D.matrix_wide ? 4u : 2u);
+    uint32_t* x = d_ctrl + kCtrlWords;
+    if (!again) {
+        HIP_CHECK(hipMemsetAsync(d_ctrl, 0, (kCtrlWords + kMgWords) * 4, st));
+        const uint64_t work = std::max<uint64_t>(n, total_bytes / 8 + 1);
+        kern::validate_batch((uint32_t)std::min<uint64_t>((work + 255) / 256, 1u << 16), st, a, total_bytes);
+        kern::marginal_lds((uint32_t)n, tok.marginal_lds_bytes(), st, D, a, b, d_list, x + kMgList);
+        kern::marginal_slab((uint32_t)std::min<uint64_t>(n, 1024), st, D, a, b, d_list, x + kMgList, x + kMgListCursor);
+    } else {
+        HIP_CHECK(hipMemsetAsync(d_ctrl + kBump, 0, 8, st));  // the first run's slabs are free again
+        b.rerun = 1;
+        kern::marginal_slab(std::min<uint32_t>(again, 1024), st, D, a, b, b.oflow_list, x + kMgOflow, x + kMgOflowCursor);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+void MarginalWorkspace::run(uint64_t n, uint64_t total_bytes, double temperature, double min_prob, uint64_t out[3]) {
+    if (n > max_sentences || total_bytes > max_bytes) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch exceeds the marginal workspace capacity");
+    out[0] = out[1] = out[2] = 0;
+    if (n == 0) return;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_CHECK(hipSetDevice(tok.device()));
+    MarginalArgs m = mg;
+    m.neg_inv_t = -1.0 / temperature;
+    m.min_prob = min_prob;
+    uint32_t h[kCtrlWords + kMgWords];
+    auto read_ctrl = [&]() {
+        HIP_CHECK(hipMemcpyAsync(h, d_ctrl, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    };
+    launch(n, total_bytes, m, 0);
+    read_ctrl();
+    out[1] = h[kCtrlWords + kMgList];
+    out[2] = h[kError];
+    if (h[kError] & kErrFatal) return;
+    const uint64_t wanted = (uint64_t)h[kCtrlWords + kMgStageCursor] | ((uint64_t)h[kCtrlWords + kMgStageCursor + 1] << 32);
+    if (wanted >= 0xFFFFFFFFull) throw Error(VBT_ERR_UNSUPPORTED, "marginal: 2^32 lattice nodes or more in one chunk of the batch (split it)");
+    if (h[kCtrlWords + kMgOflow]) {  // the staging was full for some sentences: make room for every range taken, run those again
+        grow_stage(wanted + wanted / 8 + 1024);
+        m.stage = mg.stage; m.nodes = mg.nodes; m.stage_cap = mg.stage_cap;
+        launch(n, total_bytes, m, h[kCtrlWords + kMgOflow]);
+    }
+    BatchArgs a{};
+    a.n = (uint32_t)n; a.tok_cnt = d_cnt; a.ctrl = d_ctrl;
+    kern::marginal_pack(st, a, m);
+    HIP_CHECK(hipGetLastError());
+    read_ctrl();
+    out[0] = h[kCtrlWords + kMgTotal];
+    out[2] = h[kError];
 }
 
 // ------------------------------------------------------------------ lines cut on the device (split.hip)

@@ -119,6 +119,26 @@ struct NBestArgs {
 };
 constexpr uint32_t kNBestMax = 16;
 
+// What a marginal run adds to BatchArgs (marginal.hip).  BatchArgs::tok_cnt[s] = nodes reported for sentence s.
+struct MarginalArgs {
+    double neg_inv_t;           // -1 / temperature
+    double min_prob;            // a node is reported iff its probability is positive and >= this
+    vbt_marginal_node* stage;   // node staging: a sentence takes [node_base[s], node_base[s] + tok_cnt[s]) with one atomic add on the cursor
+    uint64_t stage_cap;         // records it holds; a sentence whose range ends behind it writes nothing and files itself in oflow_list
+    unsigned long long* stage_cursor;  // records taken so far, the refused ranges included: what the staging has to hold
+    uint64_t* node_base;        // [n]
+    double* log_z;              // [n]
+    uint32_t* oflow_list;       // [n] sentences that found the staging full
+    uint32_t* oflow_count;
+    uint32_t rerun;             // the second run of those sentences: the range is node_base[s], no atomic
+    uint32_t stage_cells;       // cap of the connection-cost staging in cells (VBT_MARGINAL_STAGE_KB; 0 = what the arena has room for)
+    // packed, sentence order: sentence s owns the records nodes[node_off[s] .. node_off[s + 1])
+    uint32_t* node_off;         // [n + 1]
+    vbt_marginal_node* nodes;
+    uint32_t* tile_nodes;       // per tile of 256 sentences
+    uint32_t* totals;           // {nodes}
+};
+
 // ctrl[kTotal] total tokens; ctrl[kError] DevError flags; ctrl[kBump..+1] u64 scratch bump pointer;
 // ctrl[kTierCtrl + 2t] = number of sentences tier t passed on, ctrl[kTierCtrl + 2t + 1] = work cursor of tier t
 // ctrl[kNodeCursor] bump pointer of the candidate arrays
@@ -246,6 +266,10 @@ class Tokenizer {
     // LDS per wavefront of the N-best kernel's first tier (nbest.hip): VBT_NBEST_LDS_KB, read once when the tokenizer is created;
     // 0 sends every sentence to the slab tier
     uint32_t nbest_lds_bytes() const { return nbest_lds_bytes_; }
+    // The same of the marginal kernel (marginal.hip): VBT_MARGINAL_LDS_KB (default 32, at most 64, 0 = every lattice in a slab), and
+    // VBT_MARGINAL_STAGE_KB, a cap of a sentence's connection-cost staging (0 = none; for tests of the sweeps over blocks of steps)
+    uint32_t marginal_lds_bytes() const { return marginal_lds_bytes_; }
+    uint32_t marginal_stage_bytes() const { return marginal_stage_bytes_; }
 
   private:
     void upload_lexicon(const Lexicon& lx, DevLexicon& out);
@@ -284,6 +308,7 @@ class Tokenizer {
     mutable DevWordParams wparam_{};
     mutable void* wparam_alloc_ = nullptr;
     uint32_t nbest_lds_bytes_ = 0;
+    uint32_t marginal_lds_bytes_ = 0, marginal_stage_bytes_ = 0;
 };
 
 // Device buffers and launch sequence of one N-best run (nbest.hip): validate_batch -> the LDS tier (one wavefront per sentence) ->
@@ -313,6 +338,38 @@ class NBestWorkspace {
 
   private:
     std::vector<void*> allocs_;
+    void release();
+};
+
+// Device buffers and launch sequence of one marginal run (marginal.hip): validate_batch -> the LDS tier -> the slab tier; then, if
+// sentences found the node staging full, a larger staging and a second run of exactly those (the slab tier's kernel over their
+// list); then the pack pass.  The node count of a sentence is not bounded by its bytes, so the staging starts at
+// kMarginalNodesPerByte x max_bytes + kMarginalNodesPerSentence x max_sentences records and grows to what a run asked for; it
+// keeps its size between calls.
+constexpr uint64_t kMarginalNodesPerByte = 4, kMarginalNodesPerSentence = 64;
+class MarginalWorkspace {
+  public:
+    MarginalWorkspace(const Tokenizer& tok, uint64_t max_sentences, uint64_t max_bytes);
+    ~MarginalWorkspace();
+    MarginalWorkspace(const MarginalWorkspace&) = delete;
+    MarginalWorkspace& operator=(const MarginalWorkspace&) = delete;
+    // d_text / d_off: the workspace's own input buffers, filled by the caller on `stream`.  Runs the sweeps (twice for sentences that
+    // found the staging full) and the pack pass, waits, and returns {nodes, sentences the slab tier took, DevError flags}.
+    void run(uint64_t n, uint64_t total_bytes, double temperature, double min_prob, uint64_t out[3]);
+    const Tokenizer& tok;
+    uint64_t max_sentences, max_bytes;
+    void* stream = nullptr;
+    uint8_t* d_text = nullptr;
+    uint64_t* d_off = nullptr;
+    MarginalArgs mg{};
+    uint32_t *d_cnt = nullptr, *d_ctrl = nullptr, *d_list = nullptr, *d_tile_sums = nullptr;
+    char* d_scratch = nullptr;
+    uint64_t scratch_bytes = 0;
+
+  private:
+    std::vector<void*> allocs_;
+    void launch(uint64_t n, uint64_t total_bytes, const MarginalArgs& m, uint32_t again);  // again: sentences of the second run (0: the first run)
+    void grow_stage(uint64_t records);
     void release();
 };
 

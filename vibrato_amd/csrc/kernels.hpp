@@ -51,6 +51,14 @@ void nbest_lds(uint32_t n, uint32_t lds_bytes, hipStream_t stream, const DevDict
 void nbest_slab(uint32_t workgroups, hipStream_t stream, const DevDict& D, const BatchArgs& a, const NBestArgs& nb, const uint32_t* in_list, const uint32_t* in_count, uint32_t* cursor);
 void nbest_pack(hipStream_t stream, const BatchArgs& a, const NBestArgs& nb);
 
+// ---- marginal.hip: the posterior probability of every lattice node (forward-backward in float64, one wavefront per sentence)
+// marginal_lds / marginal_slab: the tiers as nbest's; a sentence takes its range of m.stage with one atomic add and files itself in
+// m.oflow_list when the range ends behind m.stage_cap (m.rerun: the second run of those, over that list with marginal_slab).
+// marginal_pack: tile sums, their scan (m.totals, node_off[n]) and the copy into sentence order.
+void marginal_lds(uint32_t n, uint32_t lds_bytes, hipStream_t stream, const DevDict& D, const BatchArgs& a, const MarginalArgs& m, uint32_t* out_list, uint32_t* out_count);
+void marginal_slab(uint32_t workgroups, hipStream_t stream, const DevDict& D, const BatchArgs& a, const MarginalArgs& m, const uint32_t* in_list, const uint32_t* in_count, uint32_t* cursor);
+void marginal_pack(hipStream_t stream, const BatchArgs& a, const MarginalArgs& m);
+
 // ---- pack.hip: token compaction, connector expansion
 uint32_t pack_split();  // workgroups per packing tile
 void tok_tile_scan(hipStream_t stream, const BatchArgs& a, uint32_t* tile_sums, uint32_t n_tiles);
