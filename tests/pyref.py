@@ -123,12 +123,14 @@ class PyTokenizer:
     def cost(self, right_id, left_id):
         return self.matrix[left_id * self.num_right + right_id]
 
-    def tokenize(self, text):
+    def _build(self, text):
+        """The one lattice builder (tokenizer.rs:94-199, lattice.rs:72-151) with the 1-best sweep's (min_idx, min_cost) per node.
+        Returns (nodes in insertion order, ends, the end position EOS connects from); None for an empty sentence."""
         chars = list(text)
         n = len(chars)
         cnt = self.counters
         if n == 0:  # worker.rs:50-52: nothing is computed (and nothing counted) for an empty sentence
-            return []
+            return None
         cnt["n_sentences"] += 1
         cnt["n_bytes"] += len(text.encode("utf-8"))
         cnt["n_chars"] += n
@@ -143,6 +145,7 @@ class PyTokenizer:
             if cinfo[i - 1]["idset"] & cinfo[i]["idset"]:
                 groupable[i - 1] = groupable[i] + 1
 
+        nodes = []
         ends = [[] for _ in range(n + 1)]
         ends[0].append({"right": 0, "min_cost": 0, "start_node": None})  # BOS (lattice.rs:72-83)
 
@@ -160,8 +163,11 @@ class PyTokenizer:
                 c = _wrap_i32(prev["min_cost"] + self.cost(prev["right"], left))
                 if c <= min_cost:  # ties: the last one wins
                     min_idx, min_cost = i, c
-            ends[end_word].append({"start_node": start_node, "start_word": start_word, "lex": lex, "wid": wid, "left": left, "right": right,
-                                   "min_idx": min_idx, "min_cost": _wrap_i32(min_cost + wcost)})
+            node = {"start_node": start_node, "start_word": start_word, "end": end_word, "start_byte": c2b[start_word], "end_byte": c2b[end_word],
+                    "lex": lex, "wid": wid, "left": left, "right": right, "wcost": wcost, "slot": len(ends[end_word]),
+                    "min_idx": min_idx, "min_cost": _wrap_i32(min_cost + wcost)}
+            ends[end_word].append(node)
+            nodes.append(node)
 
         def unk_words(start, has_matched, emit):  # unknown.rs:69-137
             ci = cinfo[start]
@@ -213,6 +219,28 @@ class PyTokenizer:
             start_word += 1
             start_node = start_word
 
+        return nodes, ends, start_node
+
+    def lattice(self, text):
+        """The lattice tokenize() takes its path from: {"num_chars", "nodes", "eos_from"}.  `nodes` in lattice order (start position,
+        then insertion order), each with start_node (the end position its predecessors are taken from), start_word, end, start_byte,
+        end_byte, lex, wid, left, right, wcost and slot (its index in ends[end]; slot 0 of ends[0] is BOS, right id 0);
+        `eos_from` = the end position EOS connects from (start_node after the loop, tokenizer.rs:138).  The counters stay as they were."""
+        saved = dict(self.counters)
+        built = self._build(text)
+        self.counters.clear()
+        self.counters.update(saved)
+        if built is None:
+            return {"num_chars": 0, "nodes": [], "eos_from": 0}
+        keys = ("start_node", "start_word", "end", "start_byte", "end_byte", "lex", "wid", "left", "right", "wcost", "slot")
+        return {"num_chars": len(text), "nodes": [{k: nd[k] for k in keys} for nd in built[0]], "eos_from": built[2]}
+
+    def tokenize(self, text):
+        built = self._build(text)
+        if built is None:
+            return []
+        _, ends, start_node = built
+        cnt = self.counters
         # EOS (lattice.rs:85-101) and the back-trace (lattice.rs:159-168)
         min_idx, min_cost = 0xFFFF, I32_MAX
         for i, prev in enumerate(ends[start_node]):
@@ -225,7 +253,7 @@ class PyTokenizer:
         end, idx = start_node, min_idx
         while end != 0:
             node = ends[end][idx]
-            tokens.append({"start_char": node["start_word"], "end_char": end, "start_byte": c2b[node["start_word"]], "end_byte": c2b[end],
+            tokens.append({"start_char": node["start_word"], "end_char": end, "start_byte": node["start_byte"], "end_byte": node["end_byte"],
                            "word_idx": (node["lex"] << 30) | node["wid"], "total_cost": node["min_cost"]})
             end, idx = node["start_node"], node["min_idx"]
         tokens.reverse()
