@@ -294,6 +294,36 @@ VBT_API int vbt_tokenize_mecab(const vbt_tokenizer* tok, const uint8_t* text, co
  * ids printed are the dictionary's, from a word-parameter table of the device image uploaded at the first call. */
 VBT_API int vbt_tokenize_detail(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
                                 char** out, size_t* len, uint64_t* line_off);
+/* User-defined output formats, rendered ON THE DEVICE (MeCab's --node-format / --unk-format / --bos-format / --eos-format, -F -U -B
+ * -E): per sentence the bos bytes, one expansion of `node` per token -- of `unk` for a word of the unknown lexicon -- and the eos
+ * bytes; a sentence without tokens is bos + eos.  unk == NULL: = node; bos == NULL: ""; eos == NULL: "EOS\n".  Directives, with MeCab's
+ * meanings: %m the surface; %H the whole feature string as stored (what vbt_tokenize_mecab prints); %f[i] CSV field i (from 0) of the
+ * feature, unquoted as utils::parse_csv_row (utils.rs:40-61) yields it, nothing when the feature has no field i; %f[i,j,..] those
+ * fields joined by ',' (an absent one is an empty string between the commas); %F<c>[i,j,..] those fields joined by the byte <c>,
+ * SKIPPING the fields that are absent or exactly "*"; %pw and %c the word cost, %pc the total cost, %phl / %phr the DICTIONARY's left
+ * / right id (never the device's renumbered ids); %ps %pe %pl the token's start byte, end byte and byte length in its sentence; %s 0
+ * for a system or user word, 1 for an unknown word; %% a '%'.  Escapes in all four strings: \0 \a \b \t \n \v \f \r \\ (the
+ * control bytes themselves are taken as they are).  bos and eos take literals, escapes and %% only.  Limits: 32 ops per string --
+ * a directive is one op, every index of a %f / %F list one of its own, every run of literal bytes one --, 16 distinct field indices
+ * per format, field index <= 255, 256 literal bytes per string.  Anything else -- an unknown directive or escape, an unterminated
+ * '[', an empty index list, a directive in bos or eos -- is VBT_ERR_INVALID_ARGUMENT with a message that names the string and the
+ * position.  Out of scope: %pC, %pP and the other lattice-level directives.
+ * vbt_format_check: the validation alone -- pure host code, no device; err
+ *   (optional, errcap bytes) receives the message.
+ * vbt_format_new: compiles the four strings for `tok`, which has to outlive the format.  The device side -- a field index {offset,
+ *   length} per word and wanted field, cut out of the feature table in device memory BY A KERNEL (no host pass over the feature
+ *   text; the few words with a doubled quote or bytes behind a closing quote are parsed by the host into a side blob) -- is built at
+ *   the first use, is independent of the renumbering of the connection ids, and is freed by vbt_format_free.
+ * vbt_tokenize_format: vbt_tokenize_mecab's contract in everything -- one unpipelined call, the first capacity from the largest
+ *   output-per-input ratio seen FOR THIS FORMAT OBJECT (+ 1/8 + 4 n; 8 x bytes + 4 n before any batch; VBT_FORMAT_FIRST_CAP = bytes in
+ *   the environment, read per call, overrides it), at most one re-render, *out released ONLY with vbt_free, VBT_ERR_UNSUPPORTED for
+ *   a multi-device tokenizer (sharded rendering is not implemented).  vbt_tokenize_stream does not take a format. */
+typedef struct vbt_format vbt_format;
+VBT_API int vbt_format_check(const char* node, const char* unk, const char* bos, const char* eos, char* err, size_t errcap);
+VBT_API int vbt_format_new(const vbt_tokenizer* tok, const char* node, const char* unk, const char* bos, const char* eos, vbt_format** out);
+VBT_API void vbt_format_free(vbt_format* fmt);
+VBT_API int vbt_tokenize_format(const vbt_tokenizer* tok, const vbt_format* fmt, const uint8_t* text, const uint64_t* offsets, uint64_t n,
+                                char** out, size_t* len, uint64_t* line_off);
 /* Raw bytes in -> sentences out, the lines cut ON THE DEVICE (split.hip) with the semantics of BufRead::lines(), which the
  * reference's CLI reads its input with (tokenize/src/main.rs:78-80): a line ends at '\n'; ONE '\r' directly in front of that '\n' goes
  * with it; every other '\r' is text (a lone one, the first of "\r\r\n", the last byte of an unterminated last line); an empty line is
@@ -478,6 +508,15 @@ VBT_API int vbt_workspace_render_again(vbt_workspace* ws, void* hip_stream);
 #define VBT_DETAIL_ROUND 64
 VBT_API int vbt_workspace_set_detail(vbt_workspace* ws, int enabled, int keep_records, uint64_t cap_bytes);
 VBT_API int vbt_workspace_detail(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off /* n + 1 */);
+/* Output in a compiled format on the device (vbt_format_new).  As MeCab mode -- cap_bytes, flag 32, d_line_off[n], the 64-byte pad
+ * and vbt_workspace_render_again (it serves whichever mode the last call used) are MeCab mode's, the modes share
+ * one output buffer -- with the lines of `fmt` (NULL: the mode is switched off), which has to belong to the workspace's tokenizer and
+ * to outlive the calls that use it.  One text mode at a time among the four: enabling one while another is on is
+ * VBT_ERR_INVALID_ARGUMENT.  A wave renders a sentence VBT_FORMAT_ROUND tokens at a time.
+ * vbt_workspace_format: as vbt_workspace_mecab. */
+#define VBT_FORMAT_ROUND 64
+VBT_API int vbt_workspace_set_format(vbt_workspace* ws, const vbt_format* fmt, int keep_records, uint64_t cap_bytes);
+VBT_API int vbt_workspace_format(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off /* n + 1 */);
 /* Per-call statistics (synchronizes the stream of the last call): how many sentences were filed
  * in the LDS tiers sentences are routed to up front -- the lean tier and the segment tier (n_tier0) --, in the escape tiers behind
  * them (n_tier1: what a sweep passed on) and in the list of the global-memory fallback kernel (n_tier2; a re-routed sentence is

@@ -7,7 +7,7 @@ use std::os::raw::{c_char, c_int, c_void};
 macro_rules! opaque {
     ($($name:ident),*) => { $(#[repr(C)] pub struct $name { _private: [u8; 0] })* };
 }
-opaque!(vbt_dict, vbt_tokenizer, vbt_worker, vbt_batch, vbt_workspace, vbt_nbest, vbt_marginal);
+opaque!(vbt_dict, vbt_tokenizer, vbt_worker, vbt_batch, vbt_workspace, vbt_nbest, vbt_marginal, vbt_format);
 
 pub const VBT_OK: c_int = 0;
 pub const VBT_ERR_INVALID_ARGUMENT: c_int = 1;
@@ -167,6 +167,12 @@ extern "C" {
                               line_off: *mut u64) -> c_int;
     pub fn vbt_tokenize_detail(tok: *const vbt_tokenizer, text: *const u8, offsets: *const u64, n: u64, out: *mut *mut c_char, len: *mut usize,
                                line_off: *mut u64) -> c_int;
+    pub fn vbt_format_check(node: *const c_char, unk: *const c_char, bos: *const c_char, eos: *const c_char, err: *mut c_char, errcap: usize) -> c_int;
+    pub fn vbt_format_new(tok: *const vbt_tokenizer, node: *const c_char, unk: *const c_char, bos: *const c_char, eos: *const c_char,
+                          out: *mut *mut vbt_format) -> c_int;
+    pub fn vbt_format_free(fmt: *mut vbt_format);
+    pub fn vbt_tokenize_format(tok: *const vbt_tokenizer, fmt: *const vbt_format, text: *const u8, offsets: *const u64, n: u64, out: *mut *mut c_char,
+                               len: *mut usize, line_off: *mut u64) -> c_int;
     /// The `nbest` (1 ..= 16) cheapest paths of every sentence (MeCab's `-N`); path 0 is `vbt_tokenize_batch`'s.  `*out` released with `vbt_nbest_free`.
     pub fn vbt_tokenize_nbest(tok: *const vbt_tokenizer, text: *const u8, offsets: *const u64, n: u64, nbest: u32, out: *mut *mut vbt_nbest) -> c_int;
     pub fn vbt_nbest_free(r: *mut vbt_nbest);
@@ -209,6 +215,8 @@ extern "C" {
     pub fn vbt_workspace_mecab(ws: *const vbt_workspace, d_out: *mut *const u8, d_line_off: *mut *const u64) -> c_int;
     pub fn vbt_workspace_set_detail(ws: *mut vbt_workspace, enabled: c_int, keep_records: c_int, cap_bytes: u64) -> c_int;
     pub fn vbt_workspace_detail(ws: *const vbt_workspace, d_out: *mut *const u8, d_line_off: *mut *const u64) -> c_int;
+    pub fn vbt_workspace_set_format(ws: *mut vbt_workspace, fmt: *const vbt_format, keep_records: c_int, cap_bytes: u64) -> c_int;
+    pub fn vbt_workspace_format(ws: *const vbt_workspace, d_out: *mut *const u8, d_line_off: *mut *const u64) -> c_int;
     pub fn vbt_workspace_render_again(ws: *mut vbt_workspace, hip_stream: *mut c_void) -> c_int;
     pub fn vbt_workspace_set_timing(ws: *mut vbt_workspace, enabled: c_int) -> c_int;
     pub fn vbt_workspace_count_connids(ws: *mut vbt_workspace, enabled: c_int) -> c_int;

@@ -43,6 +43,7 @@ class CallStats(C.Structure):
 WAKATI_ROUND = 256  # VBT_WAKATI_ROUND of include/vibrato_hip.h: tokens per LDS round of the wakati render kernel
 MECAB_ROUND = 128   # VBT_MECAB_ROUND: the same of the MeCab-format render kernel
 DETAIL_ROUND = 64   # VBT_DETAIL_ROUND: the same of the detail render kernel
+FORMAT_ROUND = 64   # VBT_FORMAT_ROUND: the same of the render kernel of the compiled formats
 SPLIT_TILE = 16384  # VBT_SPLIT_TILE: bytes per workgroup of the line-cutting kernels
 
 # name -> (restype, argtypes); also the list of symbols include/vibrato_hip.h declares.
@@ -106,6 +107,10 @@ SIGNATURES = {
     "vbt_tokenize_wakati": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
     "vbt_tokenize_mecab": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
     "vbt_tokenize_detail": (_int, [_vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
+    "vbt_format_check": (_int, [_cp, _cp, _cp, _cp, _vp, _sz]),
+    "vbt_format_new": (_int, [_vp, _cp, _cp, _cp, _cp, _PP]),
+    "vbt_format_free": (None, [_vp]),
+    "vbt_tokenize_format": (_int, [_vp, _vp, _vp, _vp, _u64, _PP, C.POINTER(_sz), _vp]),
     "vbt_tokenize_nbest": (_int, [_vp, _vp, _vp, _u64, _u32, _PP]),
     "vbt_nbest_free": (None, [_vp]),
     "vbt_nbest_num_sentences": (_u64, [_vp]),
@@ -134,6 +139,8 @@ SIGNATURES = {
     "vbt_workspace_mecab": (_int, [_vp, _PP, _PP]),
     "vbt_workspace_set_detail": (_int, [_vp, _int, _int, _u64]),
     "vbt_workspace_detail": (_int, [_vp, _PP, _PP]),
+    "vbt_workspace_set_format": (_int, [_vp, _vp, _int, _u64]),
+    "vbt_workspace_format": (_int, [_vp, _PP, _PP]),
     "vbt_workspace_render_again": (_int, [_vp, _vp]),
     "vbt_workspace_set_timing": (_int, [_vp, _int]),
     "vbt_workspace_count_connids": (_int, [_vp, _int]),

@@ -197,6 +197,39 @@ class Token:
                 f"lex_type={LEX_NAMES[self.lex_type]}, total_cost={self.total_cost})")
 
 
+class Format:
+    """A compiled output format of one tokenizer (Tokenizer.compile_format; vbt_format_new): what tokenize_format and
+    Workspace.set_format render on the device."""
+
+    def __init__(self, tokenizer, node, unk=None, bos="", eos="EOS\n", _cached=False):
+        # the format borrows the tokenizer and keeps it alive -- except a format the tokenizer caches itself (tokenize_format with
+        # a str): that one holds no reference back (no cycle), and the tokenizer frees it in front of its own handle
+        self._tok = None if _cached else tokenizer
+        h = C.c_void_p()
+        N.check(N.lib().vbt_format_new(tokenizer._handle(), _b(node), None if unk is None else _b(unk), _b(bos), _b(eos), C.byref(h)))
+        self._h = h
+
+    def _free(self):
+        if getattr(self, "_h", None):
+            N.lib().vbt_format_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self._free()
+        except Exception:  # interpreter teardown: module globals may be gone
+            pass
+
+
+def format_check(node, unk=None, bos="", eos="EOS\n"):
+    """Validates the four strings of a format (vbt_format_check: host code, no device); raises VibratoError(InvalidArgument) with
+    the string and the position of what is wrong."""
+    err = C.create_string_buffer(512)
+    rc = N.lib().vbt_format_check(_b(node), None if unk is None else _b(unk), _b(bos), _b(eos), err, len(err))
+    if rc != 0:
+        raise VibratoError(rc, err.value.decode("utf-8", "replace"))
+
+
 class Tokenizer:
     """vibrato::Tokenizer (tokenizer.rs:13-84). Creating one uploads the dictionary image to the GPU."""
 
@@ -212,6 +245,7 @@ class Tokenizer:
         self._h = None
         self._dict = None
         self._build_lock = threading.Lock()
+        self._formats = {}  # format strings given to tokenize_format -> Format
 
     @classmethod
     def new(cls, dictionary, device=-1, devices=None):
@@ -254,6 +288,8 @@ class Tokenizer:
 
     def __del__(self):
         try:
+            for f in getattr(self, "_formats", {}).values():  # the cached formats first: they were compiled for this handle
+                f._free()
             if getattr(self, "_h", None):
                 N.lib().vbt_tokenizer_free(self._h)
                 self._h = None
@@ -388,6 +424,24 @@ class Tokenizer:
         bytes of tokenize_batch(...).format("detail") without token records or host formatter threads.  Returns as tokenize_wakati
         does.  Single-device tokenizers only."""
         return self._tokenize_text(N.lib().vbt_tokenize_detail, sentences, text, offsets, with_offsets)
+
+    def compile_format(self, node, unk=None, bos="", eos="EOS\n"):
+        """MeCab's --node-format / --unk-format / --bos-format / --eos-format compiled for this tokenizer (vbt_format_new; the
+        directives: include/vibrato_hip.h): per sentence `bos`, per token `node` -- `unk` (default: node) for an unknown word --,
+        then `eos`.  The format's field index is cut out of the feature table on the device at its first use."""
+        return Format(self, node, unk, bos, eos)
+
+    def tokenize_format(self, sentences=None, fmt=None, text=None, offsets=None, with_offsets=False):
+        """Host text in -> text in the format `fmt` out, rendered on the device (vbt_tokenize_format).  fmt: a Format of this
+        tokenizer, or a node-format string, which is compiled once and kept.  Returns as tokenize_wakati does.  Single-device
+        tokenizers only."""
+        if not isinstance(fmt, Format):
+            if fmt is None:
+                raise VibratoError(1, "tokenize_format: no format")
+            if fmt not in self._formats:
+                self._formats[fmt] = Format(self, fmt, _cached=True)
+            fmt = self._formats[fmt]
+        return self._tokenize_text(lambda h, *a: N.lib().vbt_tokenize_format(h, fmt._h, *a), sentences, text, offsets, with_offsets)
 
     def _tokenize_text(self, call, sentences, text, offsets, with_offsets):
         if sentences is not None:
@@ -911,6 +965,18 @@ class Workspace:
         """As mecab_ptrs, of the last run() in detail mode."""
         o, lo = C.c_void_p(), C.c_void_p()
         N.check(N.lib().vbt_workspace_detail(self._h, C.byref(o), C.byref(lo)))
+        return {"out": o.value, "line_off": lo.value}
+
+    def set_format(self, fmt, keep_records=False, cap_bytes=0):
+        """Every later run() also renders the batch in the compiled format `fmt` (a Format of this workspace's tokenizer; None: off)
+        on the device (format_ptrs), with set_mecab's arguments, capacity rule and output buffer.  Not while another text mode is on."""
+        N.check(N.lib().vbt_workspace_set_format(self._h, fmt._h if fmt is not None else None, int(keep_records), int(cap_bytes)))
+        self._format = fmt  # (kept alive while the workspace may use it)
+
+    def format_ptrs(self):
+        """As mecab_ptrs, of the last run() in format mode."""
+        o, lo = C.c_void_p(), C.c_void_p()
+        N.check(N.lib().vbt_workspace_format(self._h, C.byref(o), C.byref(lo)))
         return {"out": o.value, "line_off": lo.value}
 
     def render_again(self, stream):

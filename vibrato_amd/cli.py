@@ -1,6 +1,6 @@
 """`tokenize`-compatible command line (reference: tokenize/src/main.rs:31-132).
 
-    python -m vibrato_amd.cli -i system.dic.zst [-u user.csv] [-O mecab|wakati|detail] [-S] [-M N] < lines.txt
+    python -m vibrato_amd.cli -i system.dic.zst [-u user.csv] [-O mecab|wakati|detail] [-F FMT [-U FMT] [-B FMT] [-E FMT]] [-S] [-M N] < lines.txt
 
 -i takes what the reference's CLI takes -- a dictionary written by Dictionary::write, zstd-compressed or not
 (tokenize/src/main.rs:34,59-60) -- or a directory of MeCab-format sources (lex.csv, matrix.def, char.def, unk.def).
@@ -9,6 +9,8 @@
 written are exactly those of the reference CLI for the same mode.
 `-O marginal --temperature T [--min-prob P]` (no counterpart in the reference; MeCab's -m with -t) prints every lattice node
 whose posterior probability is at least P as `surface\\tfeature\\tprob`, then `EOS`.
+-F/--node-format (with -U/--unk-format, -B/--bos-format, -E/--eos-format; MeCab's options of those names, the directives are listed
+in include/vibrato_hip.h) replaces the output mode by a format of the caller's, rendered on the device.
 """
 import argparse
 import os
@@ -46,6 +48,10 @@ def main(argv=None, stdin=None, stdout=None):
     ap.add_argument("--compile-to", default=None, help="also write the dictionary as system.dic.zst (zstd level 19) to this path")
     ap.add_argument("-u", "--userlex-csv", default=None, help="User lexicon file.")
     ap.add_argument("-O", "--output-mode", default="mecab", choices=["mecab", "wakati", "detail", "marginal"])
+    ap.add_argument("-F", "--node-format", default=None, help="per token, e.g. '%%m\\t%%f[0]\\n' (MeCab's directives; rendered on the device, instead of -O)")
+    ap.add_argument("-U", "--unk-format", default=None, help="per unknown word (default: the node format)")
+    ap.add_argument("-B", "--bos-format", default="", help="in front of every sentence (literals and escapes)")
+    ap.add_argument("-E", "--eos-format", default="EOS\\n", help="behind every sentence (literals and escapes)")
     ap.add_argument("--temperature", type=float, default=None, help="marginal mode: P(path) ~ exp(-cost / temperature), in cost units (required there)")
     ap.add_argument("--min-prob", type=float, default=0.0, help="marginal mode: report the lattice nodes whose probability is at least this")
     ap.add_argument("-S", "--ignore-space", action="store_true", help="Ignores white spaces in input strings.")
@@ -78,7 +84,13 @@ def main(argv=None, stdin=None, stdout=None):
     import queue
     import threading
     text_on_device = tok.num_devices() == 1 or args.output_mode == "marginal"
-    if args.output_mode == "marginal":
+    if args.node_format is not None:  # (the device route beat records + a host formatter)
+        if tok.num_devices() != 1:
+            ap.error("-F needs a single-device tokenizer")
+        fmt = tok.compile_format(args.node_format, args.unk_format, args.bos_format, args.eos_format)
+        text_on_device = True
+        tokenize_text = lambda lines: tok.tokenize_format(lines, fmt)  # noqa: E731
+    elif args.output_mode == "marginal":
         if args.temperature is None:
             ap.error("-O marginal needs --temperature")
         tokenize_text = lambda lines: render_marginal(d, lines, tok.tokenize_marginal(lines, args.temperature, args.min_prob))  # noqa: E731

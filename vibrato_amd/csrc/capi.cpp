@@ -26,6 +26,7 @@
 #include <hsa/hsa_ext_amd.h>
 
 #include "engine.hpp"
+#include "format.hpp"
 
 using namespace vbt;
 
@@ -279,6 +280,7 @@ struct vbt_nbest {
     std::vector<vbt_token_rec> tokens;
 };
 struct vbt_workspace { std::unique_ptr<Workspace> w; };
+struct vbt_format { std::unique_ptr<Format> f; };
 
 struct vbt_batch {
     vbt_tokenizer* tok = nullptr;
@@ -1577,7 +1579,8 @@ int vbt_tokenize_batch(const vbt_tokenizer* tok_, const uint8_t* text, const uin
 // capacity -- from the largest output-per-input ratio the tokenizer has seen -- and a batch that does not fit (error flag 32 alone)
 // is rendered once more into a buffer of the exact size the device reported (Workspace::render_text_again), not tokenized again.
 // Detail text (detail.hip; tokenize/src/main.rs:108-123) is MeCab format's protocol with a ratio and an environment override of its own.
-enum TextMode { kTextWakati, kTextMecab, kTextDetail };
+// A compiled format (format.hip; vbt_tokenize_format) likewise, with the ratio kept by the format object.
+enum TextMode { kTextWakati, kTextMecab, kTextDetail, kTextFormat };
 
 // What a text call holds while it runs: the pinned block, the device block of a call that starts from raw bytes (vbt_tokenize_stream)
 // and the workspace go back to their pools on every path, the workspace in record mode.
@@ -1596,6 +1599,7 @@ struct TextCall {
             p->ws->set_wakati(false, false);
             p->ws->set_mecab(false, false, 0);
             p->ws->set_detail(false, false, 0);
+            p->ws->set_format(nullptr, false, 0);
             pool_give(tok, rep, std::move(p));
         }
         dev_give(tok, rep, std::move(raw));  // (waits for the block's stream first)
@@ -1616,10 +1620,15 @@ static void empty_text_result(char** out, size_t* len) {
 // exactly the rendered bytes (and the line offsets, when asked for) out.  tail: 16 pinned bytes {tokens u32, error flags u32, total
 // u64}, with n + 1 pinned line offsets behind them when line_off is set.  bad_utf8: throws the VBT_ERR_UTF8 that names the line.
 static void render_text_batch(TextMode mode, vbt_tokenizer* tok, TextCall& h, uint64_t n, uint64_t bytes, uint32_t* tail, uint64_t* line_off, char** out, size_t* len,
-                              const std::function<void(PooledWorkspace&)>& feed, const std::function<void()>& bad_utf8) {
-    const bool mecab = mode != kTextWakati;  // the capacity protocol: MeCab and detail mode
+                              const std::function<void(PooledWorkspace&)>& feed, const std::function<void()>& bad_utf8, const Format* fmt = nullptr) {
+    const bool mecab = mode != kTextWakati;  // the capacity protocol: MeCab, detail and format mode
     const bool detail = mode == kTextDetail;
-    std::atomic<uint32_t>& per_kib = detail ? tok->detail_per_kib : tok->mecab_per_kib;
+    std::atomic<uint32_t>& per_kib = fmt ? fmt->per_kib : detail ? tok->detail_per_kib : tok->mecab_per_kib;
+    auto enable = [&](PooledWorkspace& p, uint64_t cap) {
+        if (fmt) p.ws->set_format(fmt, false, cap);
+        else if (detail) p.ws->set_detail(true, false, cap);
+        else p.ws->set_mecab(true, false, cap);
+    };
     Replica& rep = h.rep;
     const bool use_sdma = results_by_sdma(tok);
     uint64_t* total = reinterpret_cast<uint64_t*>(tail + 2);
@@ -1631,11 +1640,11 @@ static void render_text_batch(TextMode mode, vbt_tokenizer* tok, TextCall& h, ui
     if (mecab) {
         // first capacity: the running maximum of output bytes per KiB of input + 1/8 + "EOS\n" per sentence; 8 x the input before
         // any batch has been seen; VBT_MECAB_FIRST_CAP (bytes, read per call: tests, A/B runs) overrides
-        // (detail mode: 16 x, VBT_DETAIL_FIRST_CAP)
+        // (detail mode: 16 x, VBT_DETAIL_FIRST_CAP; format mode: the format's own ratio, VBT_FORMAT_FIRST_CAP)
         const uint32_t r = per_kib.load(std::memory_order_relaxed);
         uint64_t cap = (r ? (bytes * r / 1024) * 9 / 8 : (detail ? 16 : 8) * bytes) + 4 * n;
-        if (const char* e = std::getenv(detail ? "VBT_DETAIL_FIRST_CAP" : "VBT_MECAB_FIRST_CAP")) { const uint64_t v = std::strtoull(e, nullptr, 10); if (v) cap = v; }
-        if (detail) p.ws->set_detail(true, false, cap); else p.ws->set_mecab(true, false, cap);
+        if (const char* e = std::getenv(fmt ? "VBT_FORMAT_FIRST_CAP" : detail ? "VBT_DETAIL_FIRST_CAP" : "VBT_MECAB_FIRST_CAP")) { const uint64_t v = std::strtoull(e, nullptr, 10); if (v) cap = v; }
+        enable(p, cap);
     } else {
         p.ws->set_wakati(true, false);
     }
@@ -1646,7 +1655,7 @@ static void render_text_batch(TextMode mode, vbt_tokenizer* tok, TextCall& h, ui
     HIPX(hipStreamSynchronize(p.stream));
     if (tail[1] & kErrUtf8) bad_utf8();
     if (mecab && tail[1] == (uint32_t)kErrWakatiCap) {  // the capacity alone: the exact need is known now -- grow, render once more
-        if (detail) p.ws->set_detail(true, false, *total); else p.ws->set_mecab(true, false, *total);
+        enable(p, std::max<uint64_t>(*total, 1));
         p.ws->render_text_again(p.stream);
         HIPX(hipMemcpyAsync(tail, p.ws->d_ctrl, 8, hipMemcpyDeviceToHost, p.stream));
         HIPX(hipStreamSynchronize(p.stream));
@@ -1679,12 +1688,14 @@ static void render_text_batch(TextMode mode, vbt_tokenizer* tok, TextCall& h, ui
 }
 
 static int tokenize_text_on_device(TextMode mode, const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len,
-                                   uint64_t* line_off) {
+                                   uint64_t* line_off, const vbt_format* fmt = nullptr) {
     return guarded([&] {
         vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
         if (!tok || !offsets || !out || !len || (!text && n && offsets[n] != offsets[0])) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (mode == kTextFormat && (!fmt || &fmt->f->tok != tok->t)) throw Error(VBT_ERR_INVALID_ARGUMENT, "vbt_tokenize_format: the format is null or was compiled for another tokenizer");
         if (tok->reps.size() > 1)
-            throw Error(VBT_ERR_UNSUPPORTED, mode == kTextDetail  ? "vbt_tokenize_detail: a multi-device tokenizer cannot render detail output (sharded rendering is not implemented)"
+            throw Error(VBT_ERR_UNSUPPORTED, mode == kTextFormat  ? "vbt_tokenize_format: a multi-device tokenizer cannot render formatted output (sharded rendering is not implemented)"
+                                             : mode == kTextDetail  ? "vbt_tokenize_detail: a multi-device tokenizer cannot render detail output (sharded rendering is not implemented)"
                                              : mode == kTextMecab ? "vbt_tokenize_mecab: a multi-device tokenizer cannot render MeCab output (sharded rendering is not implemented)"
                                                                   : "vbt_tokenize_wakati: a multi-device tokenizer cannot render wakati output (sharded rendering is not implemented)");
         const uint64_t lo = offsets[0];
@@ -1714,7 +1725,7 @@ static int tokenize_text_on_device(TextMode mode, const vbt_tokenizer* tok_, con
             [&] {
                 for (uint64_t i = 0; i < n; ++i)
                     if (!valid_utf8(txt + offs[i], offs[i + 1] - offs[i])) throw Error(VBT_ERR_UTF8, "sentence " + std::to_string(i) + " is not valid UTF-8");
-            });
+            }, fmt ? fmt->f.get() : nullptr);
     });
 }
 
@@ -1819,6 +1830,30 @@ int vbt_tokenize_mecab(const vbt_tokenizer* tok, const uint8_t* text, const uint
 int vbt_tokenize_detail(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len, uint64_t* line_off) {
     return tokenize_text_on_device(kTextDetail, tok, text, offsets, n, out, len, line_off);
 }
+
+int vbt_tokenize_format(const vbt_tokenizer* tok, const vbt_format* fmt, const uint8_t* text, const uint64_t* offsets, uint64_t n, char** out, size_t* len,
+                        uint64_t* line_off) {
+    return tokenize_text_on_device(kTextFormat, tok, text, offsets, n, out, len, line_off, fmt);
+}
+
+int vbt_format_check(const char* node, const char* unk, const char* bos, const char* eos, char* err, size_t errcap) {
+    if (err && errcap) err[0] = 0;
+    const int rc = guarded([&] {
+        if (!node) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        (void)compile_format(node, unk, bos ? bos : "", eos ? eos : "EOS\n");
+    });
+    if (rc != VBT_OK && err && errcap) std::snprintf(err, errcap, "%s", vbt_last_error());
+    return rc;
+}
+
+int vbt_format_new(const vbt_tokenizer* tok, const char* node, const char* unk, const char* bos, const char* eos, vbt_format** out) {
+    return guarded([&] {
+        if (!tok || !node || !out) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        *out = new vbt_format{std::make_unique<Format>(*tok->t, compile_format(node, unk, bos ? bos : "", eos ? eos : "EOS\n"))};
+    });
+}
+
+void vbt_format_free(vbt_format* fmt) { delete fmt; }
 
 // Staging budget of one N-best run: nbest x (bytes + kSentenceSlack x sentences) token records of 24 bytes.  A batch is cut at
 // sentence borders into chunks that stay within it (a single sentence that does not is a chunk of its own); the packed records,
@@ -2302,6 +2337,22 @@ int vbt_workspace_set_detail(vbt_workspace* ws, int enabled, int keep_records, u
     return guarded([&] {
         if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null workspace");
         ws->w->set_detail(enabled != 0, keep_records != 0, cap_bytes);
+    });
+}
+
+int vbt_workspace_set_format(vbt_workspace* ws, const vbt_format* fmt, int keep_records, uint64_t cap_bytes) {
+    return guarded([&] {
+        if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        ws->w->set_format(fmt ? fmt->f.get() : nullptr, keep_records != 0, cap_bytes);
+    });
+}
+
+int vbt_workspace_format(const vbt_workspace* ws, const uint8_t** d_out, const uint64_t** d_line_off) {
+    return guarded([&] {
+        if (!ws) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (!ws->w->d_mecab) throw Error(VBT_ERR_INVALID_STATE, "format output was never enabled on this workspace (vbt_workspace_set_format)");
+        if (d_out) *d_out = ws->w->d_mecab;  // (the buffer MeCab, detail and format mode share)
+        if (d_line_off) *d_line_off = ws->w->d_line_off;
     });
 }
 

@@ -529,6 +529,9 @@ void Workspace::release() {
 
 Workspace::~Workspace() { release(); }
 
+// the word parameters, for a program that prints any (uploaded at first use, as detail mode's)
+static DevWordParams format_params(const Tokenizer& tok, const Format& f) { return f.prog.uses & kFmtUsesParams ? tok.word_param_table() : DevWordParams{}; }
+
 void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n, uint64_t total_bytes, void* stream_, bool defer_pack) {
     if (n > max_sentences || total_bytes > max_bytes) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch exceeds the workspace capacity");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -546,6 +549,7 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
     has_run = true;
     mecab_ran = mecab;
     detail_ran = detail;
+    format_ran = format != nullptr;
     HIP_CHECK(hipMemsetAsync(d_ctrl, 0, (kCtrlWords + (size_t)kBlockCtrlWords) * 4, stream));  // ctrl + cctrl
     if (packed_slot && n > packed_max_s) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch has more sentences than the packed output slot holds");
     if (n == 0) {
@@ -566,6 +570,12 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
             BatchArgs a{};
             a.ctrl = d_ctrl;
             kern::detail_lines(stream, a, tok.feature_table(), tok.word_param_table(), 0, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, false);
+            HIP_CHECK(hipGetLastError());
+        }
+        if (format) {
+            BatchArgs a{};
+            a.ctrl = d_ctrl;
+            kern::format_lines(stream, a, tok.feature_table(), format_params(tok, *format), format->device(), 0, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, false);
             HIP_CHECK(hipGetLastError());
         }
         return;
@@ -781,10 +791,12 @@ void Workspace::run(const uint8_t* d_text, const uint64_t* d_offsets, uint64_t n
         const bool scan_kernel = defer_pack || n_tiles > 2048 || env_u32("VBT_PACK_SCAN", 0);
         // (wakati mode: the lines are rendered from the staging regions; the records are packed only for a caller who wants both)
         // (MeCab and detail mode likewise; one text mode at a time)
-        const bool records = detail ? detail_keep : mecab ? mecab_keep : !wakati || wakati_keep;
+        const bool records = format ? format_keep : detail ? detail_keep : mecab ? mecab_keep : !wakati || wakati_keep;
         if (wakati) kern::wakati_lines(stream, a, n_tiles, d_line_len, d_wakati_tiles, d_line_off, d_wakati, wakati_cap, !records);
         if (mecab) kern::mecab_lines(stream, a, tok.feature_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, !records);
         if (detail) kern::detail_lines(stream, a, tok.feature_table(), tok.word_param_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, !records);
+        if (format)
+            kern::format_lines(stream, a, tok.feature_table(), format_params(tok, *format), format->device(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap, !records);
         if (records && scan_kernel) kern::tok_tile_scan(stream, a, d_tile_sums, n_tiles);
         if (records && !defer_pack) kern::compact_tokens(stream, a, d_tile_sums, n_tiles, scan_kernel ? 1u : 0u);
         last_args = a;
@@ -844,6 +856,7 @@ void Workspace::text_mode_buffers() {
 void Workspace::set_wakati(bool on, bool keep_records, uint64_t cap_limit) {
     if (on && mecab) throw Error(VBT_ERR_INVALID_ARGUMENT, "wakati mode: the workspace is in MeCab mode (one text mode at a time)");
     if (on && detail) throw Error(VBT_ERR_INVALID_ARGUMENT, "wakati mode: the workspace is in detail mode (one text mode at a time)");
+    if (on && format) throw Error(VBT_ERR_INVALID_ARGUMENT, "wakati mode: the workspace is in format mode (one text mode at a time)");
     if (on && !d_wakati) {
         HIP_CHECK(hipSetDevice(tok.device()));
         const uint64_t ns = std::max<uint64_t>(max_sentences, 1), cap = 2 * max_bytes + ns;  // bytes + tokens (<= bytes) + a byte per sentence
@@ -893,6 +906,7 @@ void Workspace::text_out_buffer(uint64_t cap_bytes) {
 void Workspace::set_mecab(bool on, bool keep_records, uint64_t cap_bytes) {
     if (on && wakati) throw Error(VBT_ERR_INVALID_ARGUMENT, "MeCab mode: the workspace is in wakati mode (one text mode at a time)");
     if (on && detail) throw Error(VBT_ERR_INVALID_ARGUMENT, "MeCab mode: the workspace is in detail mode (one text mode at a time)");
+    if (on && format) throw Error(VBT_ERR_INVALID_ARGUMENT, "MeCab mode: the workspace is in format mode (one text mode at a time)");
     if (on && cap_bytes == 0) throw Error(VBT_ERR_INVALID_ARGUMENT, "MeCab mode: cap_bytes must be > 0 (the input does not bound this output: the caller names the capacity)");
     if (on) {
         (void)tok.feature_table();  // uploaded by the first workspace that asks
@@ -905,6 +919,7 @@ void Workspace::set_mecab(bool on, bool keep_records, uint64_t cap_bytes) {
 void Workspace::set_detail(bool on, bool keep_records, uint64_t cap_bytes) {
     if (on && wakati) throw Error(VBT_ERR_INVALID_ARGUMENT, "detail mode: the workspace is in wakati mode (one text mode at a time)");
     if (on && mecab) throw Error(VBT_ERR_INVALID_ARGUMENT, "detail mode: the workspace is in MeCab mode (one text mode at a time)");
+    if (on && format) throw Error(VBT_ERR_INVALID_ARGUMENT, "detail mode: the workspace is in format mode (one text mode at a time)");
     if (on && cap_bytes == 0) throw Error(VBT_ERR_INVALID_ARGUMENT, "detail mode: cap_bytes must be > 0 (the input does not bound this output: the caller names the capacity)");
     if (on) {
         (void)tok.feature_table();  // both uploaded by the first workspace that asks
@@ -915,15 +930,33 @@ void Workspace::set_detail(bool on, bool keep_records, uint64_t cap_bytes) {
     detail_keep = on && keep_records;
 }
 
+void Workspace::set_format(const Format* fmt, bool keep_records, uint64_t cap_bytes) {
+    if (fmt && wakati) throw Error(VBT_ERR_INVALID_ARGUMENT, "format mode: the workspace is in wakati mode (one text mode at a time)");
+    if (fmt && mecab) throw Error(VBT_ERR_INVALID_ARGUMENT, "format mode: the workspace is in MeCab mode (one text mode at a time)");
+    if (fmt && detail) throw Error(VBT_ERR_INVALID_ARGUMENT, "format mode: the workspace is in detail mode (one text mode at a time)");
+    if (fmt && &fmt->tok != &tok) throw Error(VBT_ERR_INVALID_ARGUMENT, "format mode: the format was compiled for another tokenizer");
+    if (fmt && cap_bytes == 0) throw Error(VBT_ERR_INVALID_ARGUMENT, "format mode: cap_bytes must be > 0 (the input does not bound this output: the caller names the capacity)");
+    if (fmt) {
+        (void)tok.feature_table();  // uploaded / built by the first workspace that asks
+        (void)format_params(tok, *fmt);
+        (void)fmt->device();
+        text_out_buffer(cap_bytes);
+    }
+    format = fmt;
+    format_keep = fmt && keep_records;
+}
+
 void Workspace::render_text_again(void* stream_) {
-    const bool as_mecab = mecab && mecab_ran, as_detail = detail && detail_ran;
-    if (!as_mecab && !as_detail) throw Error(VBT_ERR_INVALID_STATE, "render_text_again: the last run() of this workspace was not in MeCab or detail mode");
+    const bool as_mecab = mecab && mecab_ran, as_detail = detail && detail_ran, as_format = format && format_ran;
+    if (!as_mecab && !as_detail && !as_format) throw Error(VBT_ERR_INVALID_STATE, "render_text_again: the last run() of this workspace was not in MeCab, detail or format mode");
     HIP_CHECK(hipSetDevice(tok.device()));
     last_stream = stream_;
     BatchArgs a = last_args;
     if (last_n == 0) { a = BatchArgs{}; a.ctrl = d_ctrl; }
     const uint32_t n_tiles = (uint32_t)((last_n + kScanTile - 1) / kScanTile);
-    if (as_mecab) kern::mecab_render_again(reinterpret_cast<hipStream_t>(stream_), a, tok.feature_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap);
+    if (as_format)
+        kern::format_render_again(reinterpret_cast<hipStream_t>(stream_), a, tok.feature_table(), format_params(tok, *format), format->device(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap);
+    else if (as_mecab) kern::mecab_render_again(reinterpret_cast<hipStream_t>(stream_), a, tok.feature_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap);
     else kern::detail_render_again(reinterpret_cast<hipStream_t>(stream_), a, tok.feature_table(), tok.word_param_table(), n_tiles, d_mecab_len, d_wakati_tiles, d_line_off, d_mecab, mecab_cap);
     HIP_CHECK(hipGetLastError());
 }

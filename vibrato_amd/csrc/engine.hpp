@@ -221,6 +221,7 @@ void split_count(const uint8_t* d_raw, uint64_t len, bool final, void* d_scratch
 void split_scatter(const uint8_t* d_raw, uint64_t len, const SplitInfo& info, const void* d_scratch, uint8_t* d_text, uint64_t* d_offsets, void* stream);
 
 class Workspace;
+class Format;  // format.hpp: a compiled user-defined output format
 
 class Tokenizer {
   public:
@@ -419,6 +420,12 @@ class Workspace {
     // run() used.  One text mode at a time, among the three.
     void set_detail(bool on, bool keep_records, uint64_t cap_bytes);
     bool detail = false, detail_keep = false;
+    // Format mode (format.hip): every later run() renders the batch in the compiled format `fmt` (nullptr: off) --
+    // per sentence its bos bytes, per token the node (or unk) program, its eos bytes.  MeCab mode's buffers, capacity protocol and
+    // render_text_again; one text mode at a time, among the four.  The format has to outlive the runs that use it.
+    void set_format(const Format* fmt, bool keep_records, uint64_t cap_bytes);
+    const Format* format = nullptr;
+    bool format_keep = false;
     uint8_t* d_mecab = nullptr;
     uint64_t mecab_cap = 0, mecab_alloc = 0;  // bytes the kernels may use / bytes the buffer holds in front of its pad
     void* packed_slot = nullptr;
@@ -475,6 +482,7 @@ class Workspace {
     uint64_t* d_mecab_len = nullptr;     // MeCab mode: bytes per line (d_wakati_tiles and d_line_off serve both text modes)
     bool mecab_ran = false;              // the last run() rendered MeCab text: render_text_again may follow
     bool detail_ran = false;             // ... or detail text
+    bool format_ran = false;             // ... or text in a compiled format
 
   private:
     void text_mode_buffers();  // d_wakati_tiles, d_line_off: allocated by the text mode that is enabled first

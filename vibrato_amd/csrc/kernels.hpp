@@ -1,9 +1,10 @@
-// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip, wakati.hip, mecab.hip, detail.hip, split.hip), as plain
+// Launchers of the device kernels (one translation unit per kernel family: gen.hip, lattice.hip, fused.hip, pack.hip, wakati.hip, mecab.hip, detail.hip, format.hip, split.hip), as plain
 // functions the host side (engine.hip: Tokenizer, Workspace) calls.  Every launcher enqueues on `stream` and returns.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "engine.hpp"
+#include "format.hpp"
 
 namespace vbt {
 
@@ -100,6 +101,19 @@ void detail_lines(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, 
                   uint64_t* line_off, uint8_t* out, uint64_t out_cap, bool count_tokens);
 void detail_render_again(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, const DevWordParams& w, uint32_t n_tiles, const uint64_t* line_len,
                          const uint64_t* tile_bytes, uint64_t* line_off, uint8_t* out, uint64_t out_cap);
+
+// ---- format.hip: the text of a batch in a compiled format (format.hpp) -- per sentence bos, the node / unk program per token, eos.
+// format_index: the format's field index (index[rows][slots]) cut out of the feature blob `f`; exc[0] = rows on the exception list
+// (the host parses them), exc[1 ..] those rows (rows + 1 words).  format_plan -> text_tile_scan -> format_render, with the buffers,
+// the capacity rule and the flag of mecab_lines; format_render_again as mecab_render_again.  `w` is read only by a program with
+// kFmtUsesParams.
+void format_index(hipStream_t stream, const DevFeatures& f, uint32_t rows, const FmtProgram& prog, uint2* index, uint32_t* exc);
+// index[exc[1 + i]][s] = patch[i][s] for the n_exc rows of the exception list: the entries the host made for them, in one launch
+void format_patch(hipStream_t stream, uint2* index, const uint32_t* exc, const uint2* patch, uint32_t n_exc, uint32_t slots, uint32_t rows);
+void format_lines(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, const DevWordParams& w, const DevFormat& d, uint32_t n_tiles, uint64_t* line_len,
+                  uint64_t* tile_bytes, uint64_t* line_off, uint8_t* out, uint64_t out_cap, bool count_tokens);
+void format_render_again(hipStream_t stream, const BatchArgs& a, const DevFeatures& f, const DevWordParams& w, const DevFormat& d, uint32_t n_tiles,
+                         const uint64_t* line_len, const uint64_t* tile_bytes, uint64_t* line_off, uint8_t* out, uint64_t out_cap);
 
 // ---- split.hip: raw bytes cut into sentences (BufRead::lines(): '\n' and "\r\n" end a line) over tiles of VBT_SPLIT_TILE bytes.
 // raw: 16-byte aligned, readable up to the next multiple of 16 behind len.  split_count (count pass + scan of the tiles): tiles[t]
