@@ -426,6 +426,53 @@ VBT_API int vbt_marginal_arrays(const vbt_marginal* r, const uint64_t** node_off
 /* Sentences of the call whose lattice did not fit the LDS tier and was built in global memory (observability; MeCab's -m; lattice.rs:129-151). */
 VBT_API uint64_t vbt_marginal_slab_sentences(const vbt_marginal* r);
 
+/* ---- Sampled segmentations (new: forward filtering / backward sampling over the lattice of the marginals) -------- */
+
+typedef struct vbt_sample vbt_sample;
+/* Host text in -> n_samples whole paths per sentence out, in host memory: independent draws, with repetition, from
+ * P(path) = exp(-cost / temperature) / Z over the lattice vbt_tokenize_marginal states (same candidates in insertion order, unknown
+ * words, user lexicon, ignore_space, max_grouping_len, the EOS step; sample.hip).  The cost of a path is the EXACT
+ * integer sum and does not wrap: path_cost is int64.  total_cost inside a record stays i32: it is accumulated along the path and
+ * wraps as vbt_tokenize_nbest's does.  A sentence with a path yields exactly n_samples paths; an empty sentence none; a sentence of
+ * skipped spaces only n_samples paths of no tokens with log_z = 0.  log_z = alpha(EOS), as vbt_tokenize_marginal reports it.
+ *
+ * The draw is part of the contract.  Sample r of the sentence with index s -- counted over the whole call, not within a chunk --
+ * walks from EOS to BOS.  Draw number t (0 at EOS, + 1 per token) chooses the predecessor of the current node c among the np
+ * entries of c's predecessor end list, in end-list (= insertion) order, with weights p_j = exp(alpha_j - conn(j, c) / T - L_c),
+ * L_c = LSE_j(alpha_j - conn(j, c) / T) (in the kernel L_c = alpha_c + w_c / T); a slot with alpha = -inf has weight 0.  The chosen
+ * j is the smallest one with sum_{i<=j} p_i > u x sum_i p_i -- the right-hand sum is the computed one, not 1 -- and if rounding
+ * leaves none, the last j of positive weight.  (The kernel adds in chunks of ceil(np / 16) consecutive entries and scans the 16
+ * chunk sums; that order is fixed, so a result is reproducible bit by bit, and differs from the plain running sum only where u x
+ * sum lies within rounding of a boundary.)  u = (x + 0.5) x 2^-32, x = word 0 of Philox4x32-10 (10 rounds, multipliers 0xD2511F53
+ * and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85) with counter (lo32(s), hi32(s), r, t) and key (lo32(seed), hi32(seed)).
+ * A result depends on the text, the dictionary, the temperature, n_samples, seed and s only: not on chunking, the tier a lattice
+ * ran in, staging blocks or the renumbered device image.
+ *
+ * temperature not finite or <= 0, n_samples outside 1 .. 64: VBT_ERR_INVALID_ARGUMENT; a multi-device tokenizer:
+ * VBT_ERR_UNSUPPORTED; input contract and the other error codes as vbt_tokenize_nbest.  The batch is cut at sentence borders into
+ * chunks whose record staging -- n_samples x (bytes + 24 x sentences) records of 24 bytes -- stays within 768 MiB; nothing can
+ * overflow.  VBT_MARGINAL_LDS_KB / VBT_MARGINAL_STAGE_KB apply as for vbt_tokenize_marginal.  The workspace is kept by the tokenizer
+ * between calls, and calls on one tokenizer take turns. */
+VBT_API int vbt_tokenize_sample(const vbt_tokenizer* tok, const uint8_t* text, const uint64_t* offsets, uint64_t n,
+                                double temperature, uint32_t n_samples, uint64_t seed, vbt_sample** out);
+VBT_API void vbt_sample_free(vbt_sample* r);                              /* releases a result of vbt_tokenize_sample */
+VBT_API uint64_t vbt_sample_num_sentences(const vbt_sample* r);           /* sentences of the call */
+/* Paths of sentence s: the call's n_samples, or 0 for an empty sentence. */
+VBT_API uint32_t vbt_sample_num_paths(const vbt_sample* r, uint64_t sentence);
+/* Cost of sample `rank` of sentence s: the exact sum of its word and connection costs, the connection to EOS included. */
+VBT_API int vbt_sample_path_cost(const vbt_sample* r, uint64_t sentence, uint32_t rank, int64_t* cost);
+/* Its records, in sentence order, and their number; the pointer lives until vbt_sample_free. */
+VBT_API int vbt_sample_path_records(const vbt_sample* r, uint64_t sentence, uint32_t rank, const vbt_token_rec** records,
+                                    uint32_t* count);
+/* log Z of sentence s. */
+VBT_API int vbt_sample_log_z(const vbt_sample* r, uint64_t sentence, double* log_z);
+/* The five raw arrays: sentence s owns the paths [path_off[s], path_off[s + 1]) (n + 1 entries) and log_z[s] (n entries), path p
+ * the records tokens[tok_off[p] .. tok_off[p + 1]) (paths + 1 entries) and the cost path_cost[p]. */
+VBT_API int vbt_sample_arrays(const vbt_sample* r, const uint64_t** path_off, const uint64_t** tok_off,
+                              const int64_t** path_cost, const double** log_z, const vbt_token_rec** tokens);
+/* Sentences of the call whose lattice did not fit the LDS tier and was built in global memory (observability). */
+VBT_API uint64_t vbt_sample_slab_sentences(const vbt_sample* r);
+
 /* ---- Device-resident API (zero-copy; what bench.py times) ------------------------ */
 
 /* A workspace owns the device scratch + output buffers for batches of up to

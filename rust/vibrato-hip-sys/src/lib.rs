@@ -7,7 +7,7 @@ use std::os::raw::{c_char, c_int, c_void};
 macro_rules! opaque {
     ($($name:ident),*) => { $(#[repr(C)] pub struct $name { _private: [u8; 0] })* };
 }
-opaque!(vbt_dict, vbt_tokenizer, vbt_worker, vbt_batch, vbt_workspace, vbt_nbest, vbt_marginal, vbt_format);
+opaque!(vbt_dict, vbt_tokenizer, vbt_worker, vbt_batch, vbt_workspace, vbt_nbest, vbt_marginal, vbt_sample, vbt_format);
 
 pub const VBT_OK: c_int = 0;
 pub const VBT_ERR_INVALID_ARGUMENT: c_int = 1;
@@ -200,6 +200,20 @@ extern "C" {
     pub fn vbt_marginal_nodes(r: *const vbt_marginal, sentence: u64, nodes: *mut *const vbt_marginal_node, count: *mut u64) -> c_int;
     pub fn vbt_marginal_arrays(r: *const vbt_marginal, node_off: *mut *const u64, log_z: *mut *const f64, nodes: *mut *const vbt_marginal_node) -> c_int;
     pub fn vbt_marginal_slab_sentences(r: *const vbt_marginal) -> u64;
+    // ---- Sampled segmentations
+    /// `n_samples` (1 ..= 64) whole paths per sentence drawn from P(path) ~ exp(-cost / temperature); the draw is reproducible from
+    /// `seed` and a sentence's index in the call (Philox4x32-10; see the header).  `*out` released with `vbt_sample_free`.
+    pub fn vbt_tokenize_sample(tok: *const vbt_tokenizer, text: *const u8, offsets: *const u64, n: u64, temperature: f64, n_samples: u32,
+                               seed: u64, out: *mut *mut vbt_sample) -> c_int;
+    pub fn vbt_sample_free(r: *mut vbt_sample);
+    pub fn vbt_sample_num_sentences(r: *const vbt_sample) -> u64;
+    pub fn vbt_sample_num_paths(r: *const vbt_sample, sentence: u64) -> u32;
+    pub fn vbt_sample_path_cost(r: *const vbt_sample, sentence: u64, rank: u32, cost: *mut i64) -> c_int;
+    pub fn vbt_sample_path_records(r: *const vbt_sample, sentence: u64, rank: u32, records: *mut *const vbt_token_rec, count: *mut u32) -> c_int;
+    pub fn vbt_sample_log_z(r: *const vbt_sample, sentence: u64, log_z: *mut f64) -> c_int;
+    pub fn vbt_sample_arrays(r: *const vbt_sample, path_off: *mut *const u64, tok_off: *mut *const u64, path_cost: *mut *const i64,
+                             log_z: *mut *const f64, tokens: *mut *const vbt_token_rec) -> c_int;
+    pub fn vbt_sample_slab_sentences(r: *const vbt_sample) -> u64;
 
     // ---- Device-resident API
     pub fn vbt_workspace_new(tok: *const vbt_tokenizer, max_sentences: u64, max_bytes: u64, out: *mut *mut vbt_workspace) -> c_int;

@@ -126,6 +126,15 @@ SIGNATURES = {
     "vbt_marginal_nodes": (_int, [_vp, _u64, _PP, C.POINTER(_u64)]),
     "vbt_marginal_arrays": (_int, [_vp, _PP, _PP, _PP]),
     "vbt_marginal_slab_sentences": (_u64, [_vp]),
+    "vbt_tokenize_sample": (_int, [_vp, _vp, _vp, _u64, C.c_double, _u32, _u64, _PP]),
+    "vbt_sample_free": (None, [_vp]),
+    "vbt_sample_num_sentences": (_u64, [_vp]),
+    "vbt_sample_num_paths": (_u32, [_vp, _u64]),
+    "vbt_sample_path_cost": (_int, [_vp, _u64, _u32, C.POINTER(C.c_int64)]),
+    "vbt_sample_path_records": (_int, [_vp, _u64, _u32, _PP, C.POINTER(_u32)]),
+    "vbt_sample_log_z": (_int, [_vp, _u64, C.POINTER(C.c_double)]),
+    "vbt_sample_arrays": (_int, [_vp, _PP, _PP, _PP, _PP, _PP]),
+    "vbt_sample_slab_sentences": (_u64, [_vp]),
     "vbt_split_lines": (_int, [_vp, _vp, _sz, _int, _PP, _PP, C.POINTER(_u64), C.POINTER(_sz)]),
     "vbt_tokenize_stream": (_int, [_vp, _int, _vp, _sz, _int, _PP, C.POINTER(_sz), C.POINTER(_u64), C.POINTER(_sz)]),
     "vbt_workspace_new": (_int, [_vp, _u64, _u64, _PP]),

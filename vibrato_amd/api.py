@@ -406,6 +406,28 @@ class Tokenizer:
                                               len(offsets) - 1, float(temperature), float(min_prob), C.byref(h)))
         return Marginal(h)
 
+    def tokenize_sample(self, sentences=None, temperature=None, n_samples=1, seed=0, text=None, offsets=None):
+        """`n_samples` (1..64) whole paths per sentence, drawn independently from P(path) ~ exp(-cost / temperature) over the lattice of
+        tokenize_marginal (vbt_tokenize_sample: forward filtering / backward sampling on the device).  The draw is reproducible: it
+        depends on the text, the dictionary, the temperature, n_samples, `seed` and a sentence's index in the call only.  Returns a
+        Samples.  Single-device tokenizers only."""
+        if sentences is not None:
+            enc = [_b(s) for s in sentences]
+            offsets = np.zeros(len(enc) + 1, dtype=np.uint64)
+            if enc:
+                offsets[1:] = np.cumsum([len(e) for e in enc])
+            text = np.frombuffer(b"".join(enc), dtype=np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if temperature is None:
+            raise VibratoError(1, "vbt_tokenize_sample: temperature must be finite and > 0")
+        if not 0 <= int(n_samples) < 1 << 32:
+            raise VibratoError(1, "vbt_tokenize_sample: n_samples must be 1 .. 64")
+        h = C.c_void_p()
+        N.check(N.lib().vbt_tokenize_sample(self._handle(), text.ctypes.data if text.size else None, offsets.ctypes.data,
+                                            len(offsets) - 1, float(temperature), int(n_samples), int(seed) & (2**64 - 1), C.byref(h)))
+        return Samples(h)
+
     def tokenize_wakati(self, sentences=None, text=None, offsets=None, with_offsets=False):
         """Host text in -> wakati text out (tokenize/src/main.rs:96-103), rendered on the device (vbt_tokenize_wakati): the bytes of
         tokenize_batch(...).format("wakati") without token records or host formatter threads.  Returns bytes, or with
@@ -737,6 +759,59 @@ class NBest:
     def slab_sentences(self):
         """Sentences whose lattice left the kernel's LDS tier for global memory (observability)."""
         return N.lib().vbt_nbest_slab_sentences(self._h)
+
+
+class Samples:
+    """Results of Tokenizer.tokenize_sample (host memory): n_samples sampled paths and log Z per sentence."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                N.lib().vbt_sample_free(self._h)
+                self._h = None
+        except Exception:  # interpreter teardown: module globals may be gone
+            pass
+
+    def __len__(self):
+        return N.lib().vbt_sample_num_sentences(self._h)
+
+    def num_paths(self, s):
+        return N.lib().vbt_sample_num_paths(self._h, s)
+
+    def path(self, s, r):
+        """(cost, records[TOKEN_DTYPE]) of sample r of sentence s: the exact cost of the path; the records' total_cost runs along it in i32."""
+        cost, p, cnt = C.c_int64(), C.c_void_p(), C.c_uint32()
+        N.check(N.lib().vbt_sample_path_cost(self._h, s, r, C.byref(cost)))
+        N.check(N.lib().vbt_sample_path_records(self._h, s, r, C.byref(p), C.byref(cnt)))
+        recs = np.frombuffer(C.string_at(p, cnt.value * TOKEN_DTYPE.itemsize), dtype=TOKEN_DTYPE).copy() if cnt.value else np.zeros(0, TOKEN_DTYPE)
+        return cost.value, recs
+
+    def log_z(self, s):
+        z = C.c_double()
+        N.check(N.lib().vbt_sample_log_z(self._h, s, C.byref(z)))
+        return z.value
+
+    def arrays(self):
+        """(path_off[u64, n + 1], tok_off[u64, paths + 1], path_cost[i64, paths], log_z[f8, n], tokens[TOKEN_DTYPE]) copies: sentence s
+        owns the paths path_off[s]:path_off[s + 1], path p the records tok_off[p]:tok_off[p + 1]."""
+        po, to, pc, lz, pt = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        N.check(N.lib().vbt_sample_arrays(self._h, C.byref(po), C.byref(to), C.byref(pc), C.byref(lz), C.byref(pt)))
+        n = len(self)
+        path_off = np.frombuffer(C.string_at(po, (n + 1) * 8), dtype=np.uint64).copy()
+        paths = int(path_off[-1])
+        tok_off = np.frombuffer(C.string_at(to, (paths + 1) * 8), dtype=np.uint64).copy()
+        t = int(tok_off[-1])
+        cost = np.frombuffer(C.string_at(pc, paths * 8), dtype=np.int64).copy() if paths else np.zeros(0, np.int64)
+        log_z = np.frombuffer(C.string_at(lz, n * 8), dtype=np.float64).copy() if n else np.zeros(0, np.float64)
+        toks = np.frombuffer(C.string_at(pt, t * TOKEN_DTYPE.itemsize), dtype=TOKEN_DTYPE).copy() if t else np.zeros(0, TOKEN_DTYPE)
+        return path_off, tok_off, cost, log_z, toks
+
+    def slab_sentences(self):
+        """Sentences whose lattice left the kernel's LDS tier for global memory (observability)."""
+        return N.lib().vbt_sample_slab_sentences(self._h)
 
 
 class Marginal:

@@ -12,13 +12,13 @@ LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "libvibrato_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # host code, then the kernels: gen.hip (validate_batch, generators, work lists), lattice.hip (the sweep, the resident Worker
-# kernel), fused.hip (the single-kernel fallback), pack.hip (token compaction, connector expansion), wakati.hip (segmented text rendered on the device), mecab.hip (MeCab-format text rendered on the device), detail.hip (detail text rendered on the device), format.cpp + format.hip (user-defined output formats: their compiler, and the field index and the lines rendered on the device), split.hip (raw bytes cut into lines on the device), nbest.hip (the K best paths per sentence), marginal.hip (the posterior probability of every lattice node), engine.hip (Tokenizer, Workspace)
-SOURCES = ["dict.cpp", "connector.cpp", "dictio.cpp", "format.cpp", "capi.cpp", "engine.hip", "gen.hip", "lattice.hip", "fused.hip", "pack.hip", "wakati.hip", "mecab.hip", "detail.hip", "format.hip", "split.hip", "nbest.hip", "marginal.hip"]
+# kernel), fused.hip (the single-kernel fallback), pack.hip (token compaction, connector expansion), wakati.hip (segmented text rendered on the device), mecab.hip (MeCab-format text rendered on the device), detail.hip (detail text rendered on the device), format.cpp + format.hip (user-defined output formats: their compiler, and the field index and the lines rendered on the device), split.hip (raw bytes cut into lines on the device), nbest.hip (the K best paths per sentence), marginal.hip (the posterior probability of every lattice node), sample.hip (whole paths sampled from that distribution), engine.hip (Tokenizer, Workspace)
+SOURCES = ["dict.cpp", "connector.cpp", "dictio.cpp", "format.cpp", "capi.cpp", "engine.hip", "gen.hip", "lattice.hip", "fused.hip", "pack.hip", "wakati.hip", "mecab.hip", "detail.hip", "format.hip", "split.hip", "nbest.hip", "marginal.hip", "sample.hip"]
 # every header under csrc/ (sweep_asm.hpp -- the hottest code -- was once missing from a hand-written list) + the C ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + ["../../include/vibrato_hip.h"]
-# per source file, on top of FLAGS (wakati.hip, mecab.hip, detail.hip, format.hip, split.hip, nbest.hip, marginal.hip: the packed fp32 instructions stay out of new device code)
+# per source file, on top of FLAGS (wakati.hip, mecab.hip, detail.hip, format.hip, split.hip, nbest.hip, marginal.hip, sample.hip: the packed fp32 instructions stay out of new device code)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"wakati.hip": NO_PACKED_FP32, "mecab.hip": NO_PACKED_FP32, "detail.hip": NO_PACKED_FP32, "format.hip": NO_PACKED_FP32, "split.hip": NO_PACKED_FP32, "nbest.hip": NO_PACKED_FP32, "marginal.hip": NO_PACKED_FP32}
+EXTRA_FLAGS = {"wakati.hip": NO_PACKED_FP32, "mecab.hip": NO_PACKED_FP32, "detail.hip": NO_PACKED_FP32, "format.hip": NO_PACKED_FP32, "split.hip": NO_PACKED_FP32, "nbest.hip": NO_PACKED_FP32, "marginal.hip": NO_PACKED_FP32, "sample.hip": NO_PACKED_FP32}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-result", "-Wno-unused-function"]
 
 

@@ -9,6 +9,8 @@
 written are exactly those of the reference CLI for the same mode.
 `-O marginal --temperature T [--min-prob P]` (no counterpart in the reference; MeCab's -m with -t) prints every lattice node
 whose posterior probability is at least P as `surface\\tfeature\\tprob`, then `EOS`.
+`-O sample --temperature T [--samples N] [--seed S]` prints N segmentations per sentence drawn from P(path) ~ exp(-cost / T), one
+line of space-separated surfaces each, then `EOS` (block k of the input is drawn with seed S + the lines in front of it).
 -F/--node-format (with -U/--unk-format, -B/--bos-format, -E/--eos-format; MeCab's options of those names, the directives are listed
 in include/vibrato_hip.h) replaces the output mode by a format of the caller's, rendered on the device.
 """
@@ -42,18 +44,33 @@ def render_marginal(d, lines, mg):
     return b"".join(out)
 
 
+def render_sample(lines, sm):
+    """-O sample: per sentence one line of space-separated surfaces per sampled path, then "EOS" -- formatted here from the arrays
+    of Tokenizer.tokenize_sample."""
+    path_off, tok_off, _, _, toks = sm.arrays()
+    out = []
+    for s, line in enumerate(lines):
+        for p in range(int(path_off[s]), int(path_off[s + 1])):
+            recs = toks[int(tok_off[p]):int(tok_off[p + 1])]
+            out += [b" ".join(line[int(g["start_byte"]):int(g["end_byte"])] for g in recs), b"\n"]
+        out.append(b"EOS\n")
+    return b"".join(out)
+
+
 def main(argv=None, stdin=None, stdout=None):
     ap = argparse.ArgumentParser(prog="tokenize", description="Predicts morphemes")
     ap.add_argument("-i", "--sysdic", required=True, help="System dictionary (in zstd), or a directory with lex.csv, matrix.def, char.def, unk.def")
     ap.add_argument("--compile-to", default=None, help="also write the dictionary as system.dic.zst (zstd level 19) to this path")
     ap.add_argument("-u", "--userlex-csv", default=None, help="User lexicon file.")
-    ap.add_argument("-O", "--output-mode", default="mecab", choices=["mecab", "wakati", "detail", "marginal"])
+    ap.add_argument("-O", "--output-mode", default="mecab", choices=["mecab", "wakati", "detail", "marginal", "sample"])
     ap.add_argument("-F", "--node-format", default=None, help="per token, e.g. '%%m\\t%%f[0]\\n' (MeCab's directives; rendered on the device, instead of -O)")
     ap.add_argument("-U", "--unk-format", default=None, help="per unknown word (default: the node format)")
     ap.add_argument("-B", "--bos-format", default="", help="in front of every sentence (literals and escapes)")
     ap.add_argument("-E", "--eos-format", default="EOS\\n", help="behind every sentence (literals and escapes)")
-    ap.add_argument("--temperature", type=float, default=None, help="marginal mode: P(path) ~ exp(-cost / temperature), in cost units (required there)")
+    ap.add_argument("--temperature", type=float, default=None, help="marginal and sample mode: P(path) ~ exp(-cost / temperature), in cost units (required there)")
     ap.add_argument("--min-prob", type=float, default=0.0, help="marginal mode: report the lattice nodes whose probability is at least this")
+    ap.add_argument("--samples", type=int, default=1, help="sample mode: paths drawn per sentence (1 .. 64)")
+    ap.add_argument("--seed", type=int, default=0, help="sample mode: seed of the draw")
     ap.add_argument("-S", "--ignore-space", action="store_true", help="Ignores white spaces in input strings.")
     ap.add_argument("-M", "--max-grouping-len", type=int, default=None, help="Maximum length of unknown words.")
     ap.add_argument("--block", type=int, default=65536, help="lines per GPU batch")
@@ -83,7 +100,7 @@ def main(argv=None, stdin=None, stdout=None):
     # tokenize_mecab / tokenize_detail -- and the output stage only writes it; DESIGN.md 3.4a-c hold the measurements behind that)
     import queue
     import threading
-    text_on_device = tok.num_devices() == 1 or args.output_mode == "marginal"
+    text_on_device = tok.num_devices() == 1 or args.output_mode in ("marginal", "sample")
     if args.node_format is not None:  # (the device route beat records + a host formatter)
         if tok.num_devices() != 1:
             ap.error("-F needs a single-device tokenizer")
@@ -94,6 +111,15 @@ def main(argv=None, stdin=None, stdout=None):
         if args.temperature is None:
             ap.error("-O marginal needs --temperature")
         tokenize_text = lambda lines: render_marginal(d, lines, tok.tokenize_marginal(lines, args.temperature, args.min_prob))  # noqa: E731
+    elif args.output_mode == "sample":
+        if args.temperature is None:
+            ap.error("-O sample needs --temperature")
+        seen = [0]  # lines in front of the block (one block at a time passes the tokenize stage)
+
+        def tokenize_text(lines):
+            sm = tok.tokenize_sample(lines, args.temperature, args.samples, args.seed + seen[0])
+            seen[0] += len(lines)
+            return render_sample(lines, sm)
     else:
         tokenize_text = {"wakati": tok.tokenize_wakati, "mecab": tok.tokenize_mecab, "detail": tok.tokenize_detail}[args.output_mode]
     blocks, batches = queue.Queue(maxsize=2), queue.Queue(maxsize=2)

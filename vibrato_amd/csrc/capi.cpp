@@ -262,7 +262,10 @@ struct vbt_tokenizer {
     // vbt_tokenize_marginal: likewise
     std::mutex marginal_mu;
     std::unique_ptr<MarginalWorkspace> marginal_ws;
-    ~vbt_tokenizer() { nbest_ws.reset(); marginal_ws.reset(); for (auto& r : reps) r->pool.clear(); }  // before the Tokenizers (workspaces reference them)
+    // vbt_tokenize_sample: likewise
+    std::mutex sample_mu;
+    std::unique_ptr<SampleWorkspace> sample_ws;
+    ~vbt_tokenizer() { nbest_ws.reset(); marginal_ws.reset(); sample_ws.reset(); for (auto& r : reps) r->pool.clear(); }  // before the Tokenizers (workspaces reference them)
 };
 // Results of vbt_tokenize_marginal in host memory: sentence s owns the nodes [node_off[s], node_off[s + 1]) and log_z[s].
 struct vbt_marginal {
@@ -277,6 +280,14 @@ struct vbt_nbest {
     uint64_t n = 0, slab_sentences = 0;
     std::vector<uint64_t> path_off, tok_off;
     std::vector<int32_t> path_cost;
+    std::vector<vbt_token_rec> tokens;
+};
+// Results of vbt_tokenize_sample in host memory: laid out as vbt_nbest, the costs exact (int64), + log_z[s].
+struct vbt_sample {
+    uint64_t n = 0, slab_sentences = 0;
+    std::vector<uint64_t> path_off, tok_off;
+    std::vector<int64_t> path_cost;
+    std::vector<double> log_z;
     std::vector<vbt_token_rec> tokens;
 };
 struct vbt_workspace { std::unique_ptr<Workspace> w; };
@@ -2030,6 +2041,111 @@ int vbt_marginal_arrays(const vbt_marginal* r, const uint64_t** node_off, const 
         if (node_off) *node_off = r->node_off.data();
         if (log_z) *log_z = r->log_z.data();
         if (nodes) *nodes = r->nodes.data();
+    });
+}
+
+// Staging budget of one sampling run: n_samples x (bytes + kSentenceSlack x sentences) token records of 24 bytes, nbest's bound
+// (tokens <= bytes per sample: nothing can overflow).  A batch is cut at sentence borders into chunks that stay within it (a single
+// sentence that does not is a chunk of its own).  A draw names its sentence by the index in the whole call, so the cut does not show.
+constexpr uint64_t kSampleStageBudget = 768ull << 20;
+
+int vbt_tokenize_sample(const vbt_tokenizer* tok_, const uint8_t* text, const uint64_t* offsets, uint64_t n, double temperature, uint32_t n_samples,
+                        uint64_t seed, vbt_sample** out) {
+    return guarded([&] {
+        vbt_tokenizer* tok = const_cast<vbt_tokenizer*>(tok_);
+        if (!tok || !offsets || !out || (!text && n && offsets[n] != offsets[0])) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (!std::isfinite(temperature) || !(temperature > 0.0)) throw Error(VBT_ERR_INVALID_ARGUMENT, "vbt_tokenize_sample: temperature must be finite and > 0");
+        if (n_samples < 1 || n_samples > kSampleMax) throw Error(VBT_ERR_INVALID_ARGUMENT, "vbt_tokenize_sample: n_samples must be 1 .. 64");
+        if (tok->reps.size() > 1) throw Error(VBT_ERR_UNSUPPORTED, "vbt_tokenize_sample: a multi-device tokenizer cannot sample paths (sharding is not implemented)");
+        for (uint64_t i = 1; i <= n; ++i)
+            if (offsets[i] < offsets[i - 1]) throw Error(VBT_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
+        if (offsets[n] - offsets[0] >= 0xFFFFFFFFull || n >= 0xFFFFFFFFull) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch too large (split it)");
+        auto res = std::make_unique<vbt_sample>();
+        res->n = n;
+        res->path_off.assign(n + 1, 0);
+        res->tok_off.assign(1, 0);
+        res->log_z.assign(n, 0.0);
+        std::lock_guard<std::mutex> g(tok->sample_mu);
+        HIPX(hipSetDevice(tok->t->device()));
+        const uint64_t rec_budget = kSampleStageBudget / sizeof(vbt_token_rec) / n_samples;
+        std::vector<uint64_t> offs;
+        std::vector<uint32_t> tmp;
+        for (uint64_t s0 = 0; s0 < n;) {
+            uint64_t s1 = s0 + 1;
+            while (s1 < n && (offsets[s1 + 1] - offsets[s0]) + (uint64_t)kSentenceSlack * (s1 + 1 - s0) <= rec_budget) ++s1;
+            const uint64_t cn = s1 - s0, lo = offsets[s0], bytes = offsets[s1] - lo;
+            if (!tok->sample_ws || tok->sample_ws->max_sentences < cn || tok->sample_ws->max_bytes < bytes || tok->sample_ws->max_k < n_samples) {
+                tok->sample_ws.reset();
+                tok->sample_ws = std::make_unique<SampleWorkspace>(*tok->t, round_up_pow2(cn, 64), round_up_pow2(bytes, 4096), n_samples);
+            }
+            SampleWorkspace& ws = *tok->sample_ws;
+            hipStream_t st = reinterpret_cast<hipStream_t>(ws.stream);
+            offs.resize(cn + 1);
+            for (uint64_t i = 0; i <= cn; ++i) offs[i] = offsets[s0 + i] - lo;
+            if (bytes) HIPX(hipMemcpyAsync(ws.d_text, text + lo, bytes, hipMemcpyHostToDevice, st));
+            HIPX(hipMemcpyAsync(ws.d_off, offs.data(), (cn + 1) * 8, hipMemcpyHostToDevice, st));
+            ws.run(cn, bytes, temperature, n_samples, seed, s0);
+            uint32_t tot[4];
+            ws.totals(tot);
+            if (tot[3] & kErrUtf8)
+                for (uint64_t i = 0; i < cn; ++i)
+                    if (!valid_utf8(text + lo + offs[i], offs[i + 1] - offs[i])) throw Error(VBT_ERR_UTF8, "sentence " + std::to_string(s0 + i) + " is not valid UTF-8");
+            check_device_errors(tot[3]);
+            const uint64_t P = tot[0], T = tot[1], p0 = res->path_cost.size(), t0 = res->tokens.size();
+            res->slab_sentences += tot[2];
+            tmp.resize(std::max<uint64_t>(cn + 1, P + 1));
+            HIPX(hipMemcpyAsync(tmp.data(), ws.sp.path_off, (cn + 1) * 4, hipMemcpyDeviceToHost, st));
+            HIPX(hipStreamSynchronize(st));
+            for (uint64_t i = 0; i <= cn; ++i) res->path_off[s0 + i] = p0 + tmp[i];
+            HIPX(hipMemcpyAsync(tmp.data(), ws.sp.tok_off, (P + 1) * 4, hipMemcpyDeviceToHost, st));
+            HIPX(hipStreamSynchronize(st));
+            res->tok_off.resize(p0 + P + 1);
+            for (uint64_t i = 0; i <= P; ++i) res->tok_off[p0 + i] = t0 + tmp[i];
+            res->path_cost.resize(p0 + P);
+            res->tokens.resize(t0 + T);
+            HIPX(hipMemcpyAsync(res->log_z.data() + s0, ws.sp.log_z, cn * 8, hipMemcpyDeviceToHost, st));
+            if (P) HIPX(hipMemcpyAsync(res->path_cost.data() + p0, ws.sp.path_cost_out, P * 8, hipMemcpyDeviceToHost, st));
+            if (T) HIPX(hipMemcpyAsync(res->tokens.data() + t0, ws.sp.tokens, T * sizeof(vbt_token_rec), hipMemcpyDeviceToHost, st));
+            HIPX(hipStreamSynchronize(st));
+            s0 = s1;
+        }
+        *out = res.release();
+    });
+}
+
+void vbt_sample_free(vbt_sample* r) { delete r; }
+uint64_t vbt_sample_num_sentences(const vbt_sample* r) { return r ? r->n : 0; }
+uint32_t vbt_sample_num_paths(const vbt_sample* r, uint64_t s) { return r && s < r->n ? (uint32_t)(r->path_off[s + 1] - r->path_off[s]) : 0; }
+uint64_t vbt_sample_slab_sentences(const vbt_sample* r) { return r ? r->slab_sentences : 0; }
+int vbt_sample_path_cost(const vbt_sample* r, uint64_t s, uint32_t rank, int64_t* cost) {
+    return guarded([&] {
+        if (!r || !cost || rank >= vbt_sample_num_paths(r, s)) throw Error(VBT_ERR_INVALID_ARGUMENT, "path index out of range");
+        *cost = r->path_cost[r->path_off[s] + rank];
+    });
+}
+int vbt_sample_path_records(const vbt_sample* r, uint64_t s, uint32_t rank, const vbt_token_rec** records, uint32_t* count) {
+    return guarded([&] {
+        if (!r || !records || !count || rank >= vbt_sample_num_paths(r, s)) throw Error(VBT_ERR_INVALID_ARGUMENT, "path index out of range");
+        const uint64_t p = r->path_off[s] + rank;
+        *count = (uint32_t)(r->tok_off[p + 1] - r->tok_off[p]);
+        *records = r->tokens.data() + r->tok_off[p];
+    });
+}
+int vbt_sample_log_z(const vbt_sample* r, uint64_t s, double* log_z) {
+    return guarded([&] {
+        if (!r || !log_z || s >= r->n) throw Error(VBT_ERR_INVALID_ARGUMENT, "sentence index out of range");
+        *log_z = r->log_z[s];
+    });
+}
+int vbt_sample_arrays(const vbt_sample* r, const uint64_t** path_off, const uint64_t** tok_off, const int64_t** path_cost, const double** log_z,
+                      const vbt_token_rec** tokens) {
+    return guarded([&] {
+        if (!r) throw Error(VBT_ERR_INVALID_ARGUMENT, "null argument");
+        if (path_off) *path_off = r->path_off.data();
+        if (tok_off) *tok_off = r->tok_off.data();
+        if (path_cost) *path_cost = r->path_cost.data();
+        if (log_z) *log_z = r->log_z.data();
+        if (tokens) *tokens = r->tokens.data();
     });
 }
 

@@ -1292,6 +1292,99 @@ void MarginalWorkspace::run(uint64_t n, uint64_t total_bytes, double temperature
     out[2] = h[kError];
 }
 
+// ------------------------------------------------------------------ sampled paths (sample.hip)
+
+namespace {
+// words behind the control block: {entries of the slab tier's list, its work cursor, paths, tokens, record-staging cursor (u64)}
+enum { kSpList = 0, kSpListCursor = 1, kSpTotals = 2, kSpStageCursor = 4, kSpWords = 6 };
+}  // namespace
+
+SampleWorkspace::SampleWorkspace(const Tokenizer& t, uint64_t max_s, uint64_t max_b, uint32_t k) : tok(t), max_sentences(max_s), max_bytes(max_b), max_k(k) {
+    try {
+        HIP_CHECK(hipSetDevice(tok.device()));
+        if (max_b >= 0xFFFFFFFFull || max_s >= 0xFFFFFFFFull || k < 1 || k > kSampleMax) throw Error(VBT_ERR_INVALID_ARGUMENT, "sample workspace: batch too large (split it)");
+        const size_t ns = std::max<uint64_t>(max_s, 1), nbts = std::max<uint64_t>(max_b, 1);
+        const size_t rows = ns * k, slots = (nbts + kSentenceSlack * ns + 1) * k;
+        if (rows >= 0xFFFFFFFFull || slots >= 0xFFFFFFFFull) throw Error(VBT_ERR_INVALID_ARGUMENT, "sample workspace: batch too large (split it)");
+        auto alloc = [&](size_t bytes) {
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+            allocs_.push_back(p);
+            return p;
+        };
+        hipStream_t s;
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        stream = s;
+        d_text = static_cast<uint8_t*>(alloc(nbts + 16));
+        d_off = static_cast<uint64_t*>(alloc((ns + 1) * 8));
+        sp.stage = static_cast<vbt_token_rec*>(alloc(slots * sizeof(vbt_token_rec)));  // k samples of at most `bytes` tokens per sentence
+        sp.stage_cap = slots;
+        sp.tokens = static_cast<vbt_token_rec*>(alloc(slots * sizeof(vbt_token_rec)));
+        sp.path_base = static_cast<uint64_t*>(alloc(rows * 8));
+        sp.path_cnt = static_cast<uint32_t*>(alloc(rows * 4));
+        sp.path_cost = static_cast<int64_t*>(alloc(rows * 8));
+        sp.log_z = static_cast<double*>(alloc(ns * 8));
+        sp.path_off = static_cast<uint32_t*>(alloc((ns + 1) * 4));
+        sp.tok_off = static_cast<uint32_t*>(alloc((rows + 1) * 4));
+        sp.path_cost_out = static_cast<int64_t*>(alloc(rows * 8));
+        const size_t tiles = rows / 256 + 1;
+        sp.tile_paths = static_cast<uint32_t*>(alloc(tiles * 4));
+        sp.tile_toks = static_cast<uint32_t*>(alloc(tiles * 4));
+        d_npaths = static_cast<uint32_t*>(alloc(ns * 4));
+        d_list = static_cast<uint32_t*>(alloc(ns * 4));
+        d_tile_sums = static_cast<uint32_t*>(alloc((ns / kScanTile + 2) * 4));
+        d_ctrl = static_cast<uint32_t*>(alloc((kCtrlWords + kSpWords) * 4));
+        sp.totals = d_ctrl + kCtrlWords + kSpTotals;
+        sp.stage_cursor = reinterpret_cast<unsigned long long*>(d_ctrl + kCtrlWords + kSpStageCursor);
+        // the slab tier's arenas: ~24 bytes per lattice node + the connection-cost staging + 4 k bytes of walk state per character
+        scratch_bytes = std::min<uint64_t>(1ull << 30, std::max<uint64_t>(64ull << 20, (2048ull + 8ull * k) * nbts));
+        d_scratch = static_cast<char*>(alloc(scratch_bytes));
+    } catch (...) {
+        release();
+        throw;
+    }
+}
+
+void SampleWorkspace::release() {
+    for (void* p : allocs_) (void)hipFree(p);
+    allocs_.clear();
+    if (stream) (void)hipStreamDestroy(reinterpret_cast<hipStream_t>(stream));
+    stream = nullptr;
+}
+
+SampleWorkspace::~SampleWorkspace() { release(); }
+
+void SampleWorkspace::run(uint64_t n, uint64_t total_bytes, double temperature, uint32_t k, uint64_t seed, uint64_t sid_base) {
+    if (n > max_sentences || total_bytes > max_bytes || k < 1 || k > max_k) throw Error(VBT_ERR_INVALID_ARGUMENT, "batch exceeds the sample workspace capacity");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_CHECK(hipSetDevice(tok.device()));
+    HIP_CHECK(hipMemsetAsync(d_ctrl, 0, (kCtrlWords + kSpWords) * 4, st));
+    if (n == 0) return;
+    const DevDict& D = tok.image().dev;  // one image for every launch of the run
+    BatchArgs a{};
+    a.text = d_text; a.offsets = d_off; a.n = (uint32_t)n;
+    a.tok_cnt = d_npaths; a.ctrl = d_ctrl; a.tile_sums = d_tile_sums;
+    a.scratch = d_scratch; a.scratch_bytes = scratch_bytes;
+    SampleArgs b = sp;
+    b.neg_inv_t = -1.0 / temperature;
+    b.stage_cells = tok.marginal_stage_bytes() / (D.matrix_wide ? 4u : 2u);
+    b.k = k; b.seed = seed; b.sid_base = sid_base;
+    uint32_t* x = d_ctrl + kCtrlWords;
+    const uint64_t work = std::max<uint64_t>(n, total_bytes / 8 + 1);
+    kern::validate_batch((uint32_t)std::min<uint64_t>((work + 255) / 256, 1u << 16), st, a, total_bytes);
+    kern::sample_lds((uint32_t)n, tok.marginal_lds_bytes(), st, D, a, b, d_list, x + kSpList);
+    kern::sample_slab((uint32_t)std::min<uint64_t>(n, 1024), st, D, a, b, d_list, x + kSpList, x + kSpListCursor);
+    kern::sample_pack(st, a, b);
+    HIP_CHECK(hipGetLastError());
+}
+
+void SampleWorkspace::totals(uint32_t out[4]) {
+    uint32_t h[kCtrlWords + kSpWords];
+    HIP_CHECK(hipMemcpyAsync(h, d_ctrl, sizeof(h), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(stream)));
+    HIP_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    out[0] = h[kCtrlWords + kSpTotals]; out[1] = h[kCtrlWords + kSpTotals + 1]; out[2] = h[kCtrlWords + kSpList]; out[3] = h[kError];
+}
+
 // ------------------------------------------------------------------ lines cut on the device (split.hip)
 
 uint64_t split_scratch_bytes(uint64_t len) { return 16 + 16 * ((len + VBT_SPLIT_TILE - 1) / VBT_SPLIT_TILE); }  // SplitInfo, a uint4 per tile

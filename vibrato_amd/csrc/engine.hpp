@@ -139,6 +139,30 @@ struct MarginalArgs {
     uint32_t* totals;           // {nodes}
 };
 
+// What a sampling run adds to BatchArgs (sample.hip).  BatchArgs::tok_cnt[s] = paths of sentence s (k, or 0).
+struct SampleArgs {
+    double neg_inv_t;           // -1 / temperature
+    uint32_t stage_cells;       // cap of the connection-cost staging in cells (VBT_MARGINAL_STAGE_KB; 0 = what the arena has room for)
+    uint32_t k;                 // samples per sentence, 1 .. kSampleMax
+    uint64_t seed;              // the Philox key
+    uint64_t sid_base;          // index of the chunk's first sentence in the whole call: a draw's counter names s = sid_base + sid
+    vbt_token_rec* stage;       // record staging: a sentence takes the range of all its samples' tokens with one atomic add on the cursor
+    uint64_t stage_cap;         // records it holds: k x (bytes + kSentenceSlack x sentences), which tokens <= bytes per sample cannot exceed
+    unsigned long long* stage_cursor;
+    uint64_t* path_base;        // [n * k] where the records of sample (s, r) start in the staging, in token order
+    uint32_t* path_cnt;         // [n * k] its tokens
+    int64_t* path_cost;         // [n * k] its cost, the exact sum
+    double* log_z;              // [n] alpha(EOS)
+    // packed, sentence-major, sample-minor: sentence s owns the paths [path_off[s], path_off[s + 1]), path p the records [tok_off[p], tok_off[p + 1])
+    uint32_t* path_off;         // [n + 1]
+    uint32_t* tok_off;          // [paths + 1]
+    int64_t* path_cost_out;     // [paths]
+    vbt_token_rec* tokens;
+    uint32_t *tile_paths, *tile_toks;  // per tile of 256 rows (s, r)
+    uint32_t* totals;           // {paths, tokens}
+};
+constexpr uint32_t kSampleMax = 64;
+
 // ctrl[kTotal] total tokens; ctrl[kError] DevError flags; ctrl[kBump..+1] u64 scratch bump pointer;
 // ctrl[kTierCtrl + 2t] = number of sentences tier t passed on, ctrl[kTierCtrl + 2t + 1] = work cursor of tier t
 // ctrl[kNodeCursor] bump pointer of the candidate arrays
@@ -371,6 +395,36 @@ class MarginalWorkspace {
     std::vector<void*> allocs_;
     void launch(uint64_t n, uint64_t total_bytes, const MarginalArgs& m, uint32_t again);  // again: sentences of the second run (0: the first run)
     void grow_stage(uint64_t records);
+    void release();
+};
+
+// Device buffers and launch sequence of one sampling run (sample.hip): validate_batch -> the LDS tier -> the slab tier -> the pack
+// pass, with the tier knobs of the marginal kernel (the same arena and staging).  Holds batches of up to max_sentences / max_bytes
+// at up to max_k samples per sentence; the record staging is max_k x (max_bytes + kSentenceSlack x max_sentences) records, nbest's
+// bound, which is what the caller budgets (vbt_tokenize_sample cuts its batch into chunks by it).  Nothing can overflow.
+class SampleWorkspace {
+  public:
+    SampleWorkspace(const Tokenizer& tok, uint64_t max_sentences, uint64_t max_bytes, uint32_t max_k);
+    ~SampleWorkspace();
+    SampleWorkspace(const SampleWorkspace&) = delete;
+    SampleWorkspace& operator=(const SampleWorkspace&) = delete;
+    // d_text / d_off: the workspace's own input buffers, filled by the caller on `stream`; sid_base: the index of the chunk's first sentence
+    void run(uint64_t n, uint64_t total_bytes, double temperature, uint32_t k, uint64_t seed, uint64_t sid_base);  // asynchronous on `stream`
+    // waits for the run; {paths, tokens, sentences the slab tier took, DevError flags}
+    void totals(uint32_t out[4]);
+    const Tokenizer& tok;
+    uint64_t max_sentences, max_bytes;
+    uint32_t max_k;
+    void* stream = nullptr;
+    uint8_t* d_text = nullptr;
+    uint64_t* d_off = nullptr;
+    SampleArgs sp{};
+    uint32_t *d_npaths = nullptr, *d_ctrl = nullptr, *d_list = nullptr, *d_tile_sums = nullptr;
+    char* d_scratch = nullptr;
+    uint64_t scratch_bytes = 0;
+
+  private:
+    std::vector<void*> allocs_;
     void release();
 };
 

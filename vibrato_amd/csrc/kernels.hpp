@@ -60,6 +60,14 @@ void marginal_lds(uint32_t n, uint32_t lds_bytes, hipStream_t stream, const DevD
 void marginal_slab(uint32_t workgroups, hipStream_t stream, const DevDict& D, const BatchArgs& a, const MarginalArgs& m, const uint32_t* in_list, const uint32_t* in_count, uint32_t* cursor);
 void marginal_pack(hipStream_t stream, const BatchArgs& a, const MarginalArgs& m);
 
+// ---- sample.hip: whole paths drawn from P(path) ~ exp(-cost / T) (the marginals' forward sweep, then backward sampling; one
+// wavefront per sentence).  sample_lds / sample_slab: the tiers as marginal's; a sentence takes its range of p.stage with one
+// atomic add.  sample_pack: tile sums, their scan (p.totals, path_off[n], tok_off[paths]) and the copy into sentence-major,
+// sample-minor order.
+void sample_lds(uint32_t n, uint32_t lds_bytes, hipStream_t stream, const DevDict& D, const BatchArgs& a, const SampleArgs& p, uint32_t* out_list, uint32_t* out_count);
+void sample_slab(uint32_t workgroups, hipStream_t stream, const DevDict& D, const BatchArgs& a, const SampleArgs& p, const uint32_t* in_list, const uint32_t* in_count, uint32_t* cursor);
+void sample_pack(hipStream_t stream, const BatchArgs& a, const SampleArgs& p);
+
 // ---- pack.hip: token compaction, connector expansion
 uint32_t pack_split();  // workgroups per packing tile
 void tok_tile_scan(hipStream_t stream, const BatchArgs& a, uint32_t* tile_sums, uint32_t n_tiles);
